@@ -14,6 +14,14 @@ Launch:
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line with the whole-job aggregate.
+
+A plain run does only what that line needs: set up, warm up, time
+--steps steps, print. --dump-outputs DIR additionally writes what the
+timed steps computed (losses.npy: the loss of each timed step, float64;
+params.npy: a fixed seeded sample of the parameters after the last step,
+float32) so two builds can be compared output for output; inputs and
+initial weights are seeded and identical from run to run. --full is
+reserved for measurements beyond the headline figure.
 """
 from __future__ import annotations
 
@@ -73,6 +81,41 @@ class _ListLoader:
         return iter(self.items)
 
 
+# --dump-outputs: at most this many sampled parameter values in all
+# (fp32 -> 32 MB, well inside the 64 MB the dump may take)
+_DUMP_MAX_VALUES = 8 * 2**20
+_DUMP_PER_PARAM = 32768
+
+
+def dump_outputs(out_dir, losses, model, suffix=""):
+    """Write what a caller of the timed path receives from it: the loss
+    of every timed step (the last entry is the last step's) and the
+    parameters the last optimizer step left behind. Parameters are
+    sampled per tensor at fixed seeded positions, so two builds run with
+    the same arguments dump the same positions and compare value for
+    value."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if losses is not None:
+        np.save(os.path.join(out_dir, f"losses{suffix}.npy"),
+                np.asarray([float(l) for l in losses], dtype=np.float64))
+    params = [p for p in model.parameters()]
+    per = max(1, min(_DUMP_PER_PARAM, _DUMP_MAX_VALUES // max(1, len(params))))
+    rng = np.random.default_rng(20240229)
+    chunks = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        n = flat.numel()
+        if n > per:
+            idx = torch.from_numpy(np.sort(rng.integers(0, n, size=per)))
+            flat = flat[idx.to(flat.device)]
+        chunks.append(flat.float().cpu())
+    sample = torch.cat(chunks)[:_DUMP_MAX_VALUES] if chunks \
+        else torch.zeros(0)
+    np.save(os.path.join(out_dir, f"params{suffix}.npy"),
+            sample.numpy().astype(np.float32, copy=False))
+
+
 def run_pp(args, rank, world, device, on_gpu, family, model, batches,
            labels, share_gpu=False):
     """Async pipeline-parallel bench: ONE model split into `world` stages
@@ -116,7 +159,7 @@ def run_pp(args, rank, world, device, on_gpu, family, model, batches,
                                           len(labels))]),
                 update_frequency=1,
                 model_transform=transform,
-                loss_filename="bench_pp_losses.txt")
+                loss_filename="")
     node.start()
     import torch.distributed as dist
 
@@ -145,6 +188,13 @@ def run_pp(args, rank, world, device, on_gpu, family, model, batches,
                      device=device if on_gpu and not share_gpu else "cpu")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs:
+        # every stage holds its own slice of the parameters; the leaf
+        # holds the losses
+        dump_outputs(args.dump_outputs,
+                     node.losses[-args.steps:] if node.losses else None,
+                     node.model, suffix=f"_stage{rank}")
 
     if rank == 0:
         samples_per_sec = args.micro_batch * args.steps / elapsed
@@ -201,6 +251,7 @@ def run_sp(args, rank, world, device, on_gpu, family, model, batches,
            else torch.optim.Adam(model.parameters(), lr=1e-4))
     crit = torch.nn.CrossEntropyLoss(ignore_index=-100)
     V = model.cfg.vocab_size
+    losses = []  # this rank's shard loss per step (device tensors)
 
     def step(i):
         opt.zero_grad(set_to_none=True)
@@ -210,6 +261,7 @@ def run_sp(args, rank, world, device, on_gpu, family, model, batches,
         loss.backward()
         allreduce_gradients(model)
         opt.step()
+        losses.append(loss.detach())
 
     def sync():
         if on_gpu:
@@ -230,6 +282,11 @@ def run_sp(args, rank, world, device, on_gpu, family, model, batches,
                      device=device if backend == "nccl" else "cpu")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs:
+        # parameters are replicated across the SP group; each rank's
+        # loss is the one of its sequence shard
+        dump_outputs(args.dump_outputs, losses[-args.steps:], model,
+                     suffix=f"_rank{rank}")
     if rank == 0:
         samples_per_sec = args.micro_batch * args.steps / elapsed
         print(json.dumps({
@@ -276,7 +333,19 @@ def main():
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"])
     ap.add_argument("--cpu", action="store_true",
                     help="CPU sanity mode (tiny model)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed "
+                         "(per-step losses, a fixed seeded sample of the "
+                         "updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure; a plain run only sets up, warms up, "
+                         "times the steps and prints the result line "
+                         "(there are none yet: every other configuration "
+                         "is its own --model/--parallelism invocation)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", args.gpus))
@@ -393,7 +462,9 @@ def main():
                                     for i in range(args.warmup + args.steps + nb)]),
                 update_frequency=1, reduce_factor=args.reduce_factor,
                 comm=comm, amp_dtype=amp,
-                loss_filename="bench_losses.txt")
+                # no loss log: the run writes nothing into the directory
+                # it is started from (--dump-outputs has the losses)
+                loss_filename="")
     node.start()
 
     def sync():
@@ -404,13 +475,31 @@ def main():
         if comm is not None:
             comm.barrier()
 
+    def step_is_captured():
+        gs = getattr(node.engine, "_graph_step", None)
+        return on_gpu and gs is not None and bool(gs.graphs)
+
+    def sync_between_replays():
+        # A synchronize issued from THIS thread between two replays of
+        # the captured step (the node's dispatch thread replays it on the
+        # default stream) corrupts later replays on MI355X: measured,
+        # loss and parameters turn NaN three or four steps after it,
+        # while the eager step, or the replays on a stream of their own,
+        # stay finite. It is not needed there either: the captured path
+        # enqueues the optimizer and then reads the loss back on the
+        # dispatch thread, so once wait_for_backwards() returns the
+        # stream has drained. The eager step reads the loss BEFORE the
+        # optimizer runs, so it keeps the synchronize.
+        if not step_is_captured():
+            sync()
+
     # ---- warmup ------------------------------------------------------
     for i in range(args.warmup):
         node.forward_compute(**batches[i % nb])
     node.wait_for_backwards()
-    sync()
+    sync_between_replays()
     barrier()
-    sync()
+    sync_between_replays()
 
     # ---- timed region: EXACTLY K steps -------------------------------
     t0 = time.perf_counter()
@@ -427,6 +516,12 @@ def main():
                          device=device if comm.backend == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        # each DP replica trains on its own data between averagings
+        node.join_pending_reduce()
+        dump_outputs(args.dump_outputs, node.losses[-args.steps:],
+                     node.model, suffix="" if world == 1 else f"_rank{rank}")
 
     global_batch = args.micro_batch * world
     samples_per_sec = global_batch * args.steps / elapsed
