@@ -5,6 +5,8 @@ import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
+import argparse  # noqa: E402
+
 from examples.common import node_name  # noqa: E402
 
 import torch  # noqa: E402
@@ -34,6 +36,11 @@ def synthetic_batches(vocab):
 
 if __name__ == "__main__":
     name, base_dir = node_name()
+    ap = argparse.ArgumentParser()
+    # clip gradients by their global L2 norm before each optimizer step
+    # (per pipeline stage: each stage clips its own parameter shard)
+    ap.add_argument("--max-grad-norm", type=float, default=None)
+    max_grad_norm = ap.parse_known_args()[0].max_grad_norm
     cfg = BertConfig.base()
     batches = synthetic_batches(cfg.vocab_size)
     crit = CrossEntropyLoss(-100)
@@ -42,7 +49,8 @@ if __name__ == "__main__":
                 optimizer_params={"lr": 1.76e-3},
                 criterion=lambda preds, b: crit(preds, b["labels"]),
                 labels=batches,
-                update_frequency=16)
+                update_frequency=16,
+                max_grad_norm=max_grad_norm)
     node.start()
     trainer = BertTrainer(node=node, train_loader=batches, epochs=45,
                           batch_size=BATCH)

@@ -69,9 +69,28 @@ std::tuple<at::Tensor, long, long> adam_build_table(
     std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
     std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
     std::vector<at::Tensor> masters);
+std::tuple<at::Tensor, long, long> grad_build_table(
+    std::vector<at::Tensor> gs);
+void grad_sqnorm(at::Tensor table, long nchunks, long esize,
+                 at::Tensor partials, long offset);
+void grad_norm_finalize(at::Tensor partials, long n, at::Tensor stats,
+                        double max_norm,
+                        c10::optional<at::Tensor> max_norm_buf);
+void scale_mt(at::Tensor table, long nchunks, long esize, at::Tensor gstats);
 void fused_adam_graph(at::Tensor table, long nchunks, long esize,
                       at::Tensor lr_buf, double b1, double b2, double eps,
-                      double wd, at::Tensor step_buf);
+                      double wd, at::Tensor step_buf,
+                      c10::optional<at::Tensor> gstats);
+void fused_adam_table(at::Tensor table, long nchunks, long esize, double lr,
+                      double b1, double b2, double eps, double wd, double bc1,
+                      double bc2, c10::optional<at::Tensor> gstats);
+void fused_sgd_table(at::Tensor table, long nchunks, long esize, double lr,
+                     double momentum, double wd, bool nesterov,
+                     c10::optional<at::Tensor> gstats);
+void fused_lamb_table(at::Tensor table, long nchunks, long esize,
+                      long ntensors, double lr, double b1, double b2,
+                      double eps, double wd, double bc1, double bc2,
+                      double clamp_trust, c10::optional<at::Tensor> gstats);
 void fused_adam(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
                 std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
                 std::vector<at::Tensor> masters, double lr, double b1,
@@ -158,7 +177,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_build_table", &adam_build_table,
         "prebuild the device chunk table (graph-capturable Adam)");
   m.def("fused_adam_graph", &fused_adam_graph,
-        "multi-tensor Adam with device lr/step buffers (hipGraph mode)");
+        "multi-tensor Adam with device lr/step buffers (hipGraph mode)",
+        py::arg("table"), py::arg("nchunks"), py::arg("esize"),
+        py::arg("lr_buf"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+        py::arg("wd"), py::arg("step_buf"), py::arg("gstats") = py::none());
+  m.def("mt_build_table", &adam_build_table,
+        "prebuild the device chunk table (any fused optimizer)");
+  m.def("grad_build_table", &grad_build_table,
+        "grads-only device chunk table (clip_grad_norm_)");
+  m.def("grad_sqnorm", &grad_sqnorm,
+        "multi-tensor per-chunk sum of squared grads -> partials");
+  m.def("grad_norm_finalize", &grad_norm_finalize,
+        "partials -> [norm, clip coefficient, non-finite count]",
+        py::arg("partials"), py::arg("n"), py::arg("stats"),
+        py::arg("max_norm"), py::arg("max_norm_buf") = py::none());
+  m.def("scale_mt", &scale_mt, "multi-tensor in-place g *= stats[1]");
+  m.def("fused_adam_table", &fused_adam_table,
+        "multi-tensor Adam from a prebuilt table (+ clip coefficient)",
+        py::arg("table"), py::arg("nchunks"), py::arg("esize"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+        py::arg("wd"), py::arg("bc1"), py::arg("bc2"),
+        py::arg("gstats") = py::none());
+  m.def("fused_sgd_table", &fused_sgd_table,
+        "multi-tensor SGD from a prebuilt table (+ clip coefficient)",
+        py::arg("table"), py::arg("nchunks"), py::arg("esize"),
+        py::arg("lr"), py::arg("momentum"), py::arg("wd"),
+        py::arg("nesterov"), py::arg("gstats") = py::none());
+  m.def("fused_lamb_table", &fused_lamb_table,
+        "multi-tensor LAMB from a prebuilt table (+ clip coefficient)",
+        py::arg("table"), py::arg("nchunks"), py::arg("esize"),
+        py::arg("ntensors"), py::arg("lr"), py::arg("b1"), py::arg("b2"),
+        py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2"),
+        py::arg("clamp_trust"), py::arg("gstats") = py::none());
   m.def("fused_sgd", &fused_sgd, "multi-tensor SGD+momentum");
   m.def("fused_lamb", &fused_lamb, "multi-tensor LAMB");
   m.def("fused_copy", &fused_copy, "multi-tensor device copy");

@@ -47,6 +47,18 @@ DEVINL void stv(void* p, int i, float v) {
     reinterpret_cast<float*>(p)[i] = v;
 }
 
+// global-norm clip coefficient applied to a gradient as it is loaded.
+// The product is made opaque to the optimizer (an empty asm, no
+// instruction): the compiler then contracts the arithmetic that follows
+// (g + wd*p -> fma) exactly as it does for an unscaled gradient, instead
+// of fusing or packing the scale into it. A coefficient of exactly 1 thus
+// reproduces the unclipped update bit for bit.
+DEVINL float gscaled(float g, float s) {
+  float r = g * s;
+  asm("" : "+v"(r));
+  return r;
+}
+
 template <typename T>
 DEVINL void adam_one(float& p, float g, float& m, float& v, float lr,
                      float b1, float b2, float eps, float wd, float bc1,
@@ -60,12 +72,13 @@ DEVINL void adam_one(float& p, float g, float& m, float& v, float lr,
 // vectorized: 4 elements/thread/iter with 16-byte fp32 state accesses
 // (m/v/master are the traffic; chunks are 64Ki elements so the body is
 // always aligned and the tail only exists in the last chunk)
-template <typename T>
+template <typename T, bool CLIP>
 __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
                                float b1, float b2, float eps, float wd,
                                float bc1, float bc2,
                                const float* __restrict__ lr_buf,
-                               const long long* __restrict__ step_buf) {
+                               const long long* __restrict__ step_buf,
+                               const float* __restrict__ gscale) {
   // hipGraph-capturable mode: lr and the bias-correction step come from
   // DEVICE buffers so replays see live values (host scalars would
   // freeze at capture — engine/graphstep.py)
@@ -75,6 +88,11 @@ __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
     bc1 = 1.f - __powf(b1, st);
     bc2 = 1.f - __powf(b2, st);
   }
+  // clip-by-global-norm coefficient (grad_norm_finalize_kernel). CLIP is
+  // a template flag, not a runtime branch, so that the no-clip
+  // instantiation (null gscale) carries no instruction of the option
+  float gs = 1.f;
+  if constexpr (CLIP) gs = *gscale;
   const Chunk c = chunks[blockIdx.x];
   const int n4 = c.n >> 2;
   float4* m4 = reinterpret_cast<float4*>(c.m);
@@ -95,6 +113,10 @@ __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
       const float4 gv = reinterpret_cast<const float4*>(c.g)[i];
       g[0] = gv.x; g[1] = gv.y; g[2] = gv.z; g[3] = gv.w;
       p = reinterpret_cast<const float4*>(c.p)[i];
+    }
+    if constexpr (CLIP) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = gscaled(g[j], gs);
     }
     adam_one<T>(p.x, g[0], m.x, v.x, lr, b1, b2, eps, wd, bc1, bc2);
     adam_one<T>(p.y, g[1], m.y, v.y, lr, b1, b2, eps, wd, bc1, bc2);
@@ -117,6 +139,7 @@ __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
   // scalar tail
   for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += blockDim.x) {
     float g = ldv<T>(c.g, i);
+    if constexpr (CLIP) g = gscaled(g, gs);
     float p = c.master ? c.master[i] : ldv<T>(c.p, i);
     float m = c.m[i], v = c.v[i];
     adam_one<T>(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2);
@@ -127,12 +150,16 @@ __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
   }
 }
 
-template <typename T>
+template <typename T, bool CLIP>
 __global__ void sgd_mt_kernel(const Chunk* __restrict__ chunks, float lr,
-                              float momentum, float wd, int nesterov) {
+                              float momentum, float wd, int nesterov,
+                              const float* __restrict__ gscale) {
+  float gs = 1.f;
+  if constexpr (CLIP) gs = *gscale;
   const Chunk c = chunks[blockIdx.x];
   for (int i = threadIdx.x; i < c.n; i += blockDim.x) {
     float g = ldv<T>(c.g, i);
+    if constexpr (CLIP) g = gscaled(g, gs);
     float p = c.master ? c.master[i] : ldv<T>(c.p, i);
     if (wd != 0.f) g += wd * p;
     if (momentum != 0.f) {
@@ -146,16 +173,20 @@ __global__ void sgd_mt_kernel(const Chunk* __restrict__ chunks, float lr,
 }
 
 // LAMB phase 1: update m/v, accumulate ||w||^2 and ||update||^2 per tensor
-template <typename T>
+template <typename T, bool CLIP>
 __global__ void lamb_phase1_kernel(const Chunk* __restrict__ chunks,
                                    float* __restrict__ norms,  // [T][2]
                                    float b1, float b2, float eps, float wd,
-                                   float bc1, float bc2) {
+                                   float bc1, float bc2,
+                                   const float* __restrict__ gscale) {
   __shared__ float scratch[16];
+  float gs = 1.f;
+  if constexpr (CLIP) gs = *gscale;
   const Chunk c = chunks[blockIdx.x];
   float wsq = 0.f, usq = 0.f;
   for (int i = threadIdx.x; i < c.n; i += blockDim.x) {
     float g = ldv<T>(c.g, i);
+    if constexpr (CLIP) g = gscaled(g, gs);
     float p = c.master ? c.master[i] : ldv<T>(c.p, i);
     float m = c.m[i] = b1 * c.m[i] + (1.f - b1) * g;
     float v = c.v[i] = b2 * c.v[i] + (1.f - b2) * g * g;
@@ -192,6 +223,114 @@ __global__ void lamb_phase2_kernel(const Chunk* __restrict__ chunks,
     if (c.master) c.master[i] = p;
     stv<T>(c.p, i, p);
   }
+}
+
+// ---- global-norm gradient clipping ---------------------------------
+// sum of squares of one chunk's gradients -> partials[blockIdx.x]. One
+// plain store per block and a fixed summation order (no float atomics):
+// the norm is bit-reproducible run to run. 16-byte loads (8 bf16 / 4 fp32
+// per lane per iteration) with one fp32 accumulator per vector slot, so a
+// lane adds at most 64 terms serially per accumulator on a full chunk.
+// A chunk whose base is not 16-byte aligned (a grad that is a view into
+// a larger buffer) takes the scalar path.
+template <typename T>
+__global__ void grad_sqnorm_mt_kernel(const Chunk* __restrict__ chunks,
+                                      float* __restrict__ partials) {
+  __shared__ float scratch[16];
+  constexpr int VEC = 16 / (int)sizeof(T);
+  const Chunk c = chunks[blockIdx.x];
+  float acc[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+  int done = 0;
+  if ((reinterpret_cast<unsigned long long>(c.g) & 15ull) == 0) {
+    const int nv = c.n / VEC;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < nv; i += blockDim.x) {
+      if constexpr (sizeof(T) == 2) {
+        const bf16x8 raw = reinterpret_cast<const bf16x8*>(c.g)[i];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const float g = us2f((unsigned short)raw[j]);
+          acc[j] += g * g;
+        }
+      } else {
+        const f32x4 raw = reinterpret_cast<const f32x4*>(c.g)[i];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) acc[j] += raw[j] * raw[j];
+      }
+    }
+    done = nv * VEC;
+  }
+  // scalar tail (n % VEC) or the whole misaligned chunk
+  for (int i = done + threadIdx.x; i < c.n; i += blockDim.x) {
+    const float g = ldv<T>(c.g, i);
+    acc[0] += g * g;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) s += acc[j];
+  s = block_sum(s, scratch);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// one block: fixed-order sum of the per-chunk partials, then
+//   stats[0] = ||g||_2 (before clipping)
+//   stats[1] = min(1, max_norm / (norm + 1e-6))   (torch clip_grad_norm_)
+//   stats[2] += 1 when the norm is not finite
+// max_norm comes from a device scalar when one is given, so a hipGraph
+// replay sees the live value. A NaN coefficient stays NaN, as torch's
+// clamp leaves it (error_if_nonfinite=False behaviour).
+__global__ void grad_norm_finalize_kernel(const float* __restrict__ partials,
+                                          int n,
+                                          const float* __restrict__ max_norm_buf,
+                                          float max_norm,
+                                          float* __restrict__ stats) {
+  __shared__ float scratch[16];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];
+  acc = block_sum(acc, scratch);
+  if (threadIdx.x == 0) {
+    if (max_norm_buf) max_norm = *max_norm_buf;
+    const float norm = sqrtf(acc);
+    float coef = max_norm / (norm + 1e-6f);
+    if (coef > 1.f) coef = 1.f;
+    stats[0] = norm;
+    stats[1] = coef;
+    if (!isfinite(norm)) stats[2] += 1.f;
+  }
+}
+
+// in-place multi-tensor g *= *gscale (standalone clip_grad_norm_). A
+// coefficient of exactly 1 leaves memory untouched.
+template <typename T>
+__global__ void scale_mt_kernel(const Chunk* __restrict__ chunks,
+                                const float* __restrict__ gscale) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  const float gs = *gscale;
+  if (gs == 1.f) return;
+  const Chunk c = chunks[blockIdx.x];
+  int done = 0;
+  if ((reinterpret_cast<unsigned long long>(c.g) & 15ull) == 0) {
+    const int nv = c.n / VEC;
+    for (int i = threadIdx.x; i < nv; i += blockDim.x) {
+      if constexpr (sizeof(T) == 2) {
+        bf16x8 raw = reinterpret_cast<const bf16x8*>(c.g)[i];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          raw[j] = (short)f2us(us2f((unsigned short)raw[j]) * gs);
+        reinterpret_cast<bf16x8*>(c.g)[i] = raw;
+      } else {
+        f32x4 raw = reinterpret_cast<const f32x4*>(c.g)[i];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) raw[j] *= gs;
+        reinterpret_cast<f32x4*>(c.g)[i] = raw;
+      }
+    }
+    done = nv * VEC;
+  }
+  for (int i = done + threadIdx.x; i < c.n; i += blockDim.x)
+    stv<T>(c.g, i, ldv<T>(c.g, i) * gs);
 }
 
 // build the device-side chunk table; returns element dtype size (2|4)
@@ -276,32 +415,49 @@ __global__ void copy_mt_kernel(const Chunk* __restrict__ chunks) {
 
 }  // namespace
 
-void fused_adam(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-                std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
-                std::vector<at::Tensor> masters, double lr, double b1,
-                double b2, double eps, double wd, double bc1, double bc2) {
-  if (ps.empty()) return;
-  int nchunks = 0, esize = 4;
-  auto dev_chunks = build_chunks(ps, gs, ms, vs, masters, nchunks, esize);
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (esize == 2)
-    hipLaunchKernelGGL((adam_mt_kernel<bf16_t>), dim3(nchunks), dim3(256), 0,
-                       stream,
-                       reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()),
-                       (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
-                       (float)bc1, (float)bc2, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((adam_mt_kernel<float>), dim3(nchunks), dim3(256), 0,
-                       stream,
-                       reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()),
-                       (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
-                       (float)bc1, (float)bc2, nullptr, nullptr);
-  HIP_CHECK_LAST();
+namespace {
+
+inline const Chunk* table_ptr(const at::Tensor& table) {
+  return reinterpret_cast<const Chunk*>(table.data_ptr());
 }
 
-// graph-capturable Adam: the chunk table is prebuilt ONCE (pointers are
-// stable inside a captured step: params/state outside the graph pool,
-// grads at fixed pool addresses) and lr/step live in device buffers.
+// &stats[1]: the clip coefficient written by grad_norm_finalize_kernel
+inline const float* gscale_ptr(const c10::optional<at::Tensor>& gstats) {
+  if (!gstats.has_value()) return nullptr;
+  const at::Tensor& s = *gstats;
+  TORCH_CHECK(s.is_cuda() && s.scalar_type() == at::kFloat &&
+                  s.is_contiguous() && s.numel() >= 3,
+              "grad-norm stats must be a device fp32 tensor of 3");
+  return s.data_ptr<float>() + 1;
+}
+
+// pick the <dtype, clip> instantiation of an update kernel: esize selects
+// bf16/fp32, a non-null gscale selects the clipping variant
+#define LAUNCH_UPDATE(KERNEL, esize, gscale, ...)                            \
+  do {                                                                       \
+    if ((esize) == 2 && (gscale))                                            \
+      hipLaunchKernelGGL((KERNEL<bf16_t, true>), __VA_ARGS__);               \
+    else if ((esize) == 2)                                                   \
+      hipLaunchKernelGGL((KERNEL<bf16_t, false>), __VA_ARGS__);              \
+    else if (gscale)                                                         \
+      hipLaunchKernelGGL((KERNEL<float, true>), __VA_ARGS__);                \
+    else                                                                     \
+      hipLaunchKernelGGL((KERNEL<float, false>), __VA_ARGS__);               \
+  } while (0)
+
+inline void check_table(const at::Tensor& table, long nchunks, long esize) {
+  TORCH_CHECK(table.is_cuda() && nchunks > 0 &&
+                  table.numel() == nchunks * (long)sizeof(Chunk),
+              "chunk table / nchunks mismatch");
+  TORCH_CHECK(esize == 2 || esize == 4, "esize must be 2 or 4");
+}
+
+}  // namespace
+
+// prebuilt chunk table: ONE blocking upload that several launches of the
+// same step can share (norm reduction + update), or that a captured step
+// reuses across replays (pointers are stable inside a captured step:
+// params/state outside the graph pool, grads at fixed pool addresses).
 std::tuple<at::Tensor, long, long> adam_build_table(
     std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
     std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
@@ -312,29 +468,152 @@ std::tuple<at::Tensor, long, long> adam_build_table(
   return {table, (long)nchunks, (long)esize};
 }
 
+// grads-only chunk table (standalone clip_grad_norm_): any dense grads of
+// ONE dtype, including views at unaligned offsets
+std::tuple<at::Tensor, long, long> grad_build_table(
+    std::vector<at::Tensor> gs) {
+  TORCH_CHECK(!gs.empty());
+  std::vector<Chunk> chunks;
+  const auto dt = gs[0].scalar_type();
+  TORCH_CHECK(dt == at::kBFloat16 || dt == at::kFloat,
+              "clip_grad_norm_: grads must be bf16 or fp32");
+  const int es = dt == at::kBFloat16 ? 2 : 4;
+  for (size_t t = 0; t < gs.size(); ++t) {
+    TORCH_CHECK(gs[t].is_cuda() && gs[t].device() == gs[0].device(),
+                "clip_grad_norm_: grads must live on one GPU");
+    TORCH_CHECK(gs[t].scalar_type() == dt, "mixed dtypes in one table");
+    TORCH_CHECK(gs[t].is_non_overlapping_and_dense(),
+                "clip_grad_norm_: grad must be dense");
+    const long n = gs[t].numel();
+    char* g = (char*)gs[t].data_ptr();
+    for (long off = 0; off < n; off += CHUNK) {
+      Chunk c{};
+      c.p = c.g = g + off * es;
+      c.n = (int)std::min<long>(CHUNK, n - off);
+      c.tensor_idx = (int)t;
+      chunks.push_back(c);
+    }
+  }
+  if (chunks.empty())  // only zero-element grads
+    return {at::empty({0}, gs[0].options().dtype(at::kByte)), 0L, (long)es};
+  auto host = at::from_blob(chunks.data(),
+                            {(long)(chunks.size() * sizeof(Chunk))},
+                            at::TensorOptions().dtype(at::kByte));
+  return {host.to(gs[0].device()), (long)chunks.size(), (long)es};
+}
+
+// partials[offset + i] = sum of squares of chunk i's grads
+void grad_sqnorm(at::Tensor table, long nchunks, long esize,
+                 at::Tensor partials, long offset) {
+  check_table(table, nchunks, esize);
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+              partials.is_contiguous());
+  TORCH_CHECK(offset >= 0 && offset + nchunks <= partials.numel(),
+              "partials buffer too small");
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  float* out = partials.data_ptr<float>() + offset;
+  if (esize == 2)
+    hipLaunchKernelGGL((grad_sqnorm_mt_kernel<bf16_t>), dim3((int)nchunks),
+                       dim3(256), 0, stream, table_ptr(table), out);
+  else
+    hipLaunchKernelGGL((grad_sqnorm_mt_kernel<float>), dim3((int)nchunks),
+                       dim3(256), 0, stream, table_ptr(table), out);
+  HIP_CHECK_LAST();
+}
+
+// stats = [norm, clip coefficient, running non-finite count]; max_norm is
+// read from max_norm_buf (device) when given, else from the host value
+void grad_norm_finalize(at::Tensor partials, long n, at::Tensor stats,
+                        double max_norm,
+                        c10::optional<at::Tensor> max_norm_buf) {
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+              partials.is_contiguous());
+  TORCH_CHECK(n >= 0 && n <= partials.numel(), "partials buffer too small");
+  gscale_ptr(stats);  // validates the stats tensor
+  const float* mn = nullptr;
+  if (max_norm_buf.has_value()) {
+    TORCH_CHECK(max_norm_buf->is_cuda() &&
+                max_norm_buf->scalar_type() == at::kFloat &&
+                max_norm_buf->numel() >= 1);
+    mn = max_norm_buf->data_ptr<float>();
+  }
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, stream,
+                     partials.data_ptr<float>(), (int)n, mn, (float)max_norm,
+                     stats.data_ptr<float>());
+  HIP_CHECK_LAST();
+}
+
+// in-place g *= stats[1] over a grads-only (or full) chunk table
+void scale_mt(at::Tensor table, long nchunks, long esize, at::Tensor gstats) {
+  check_table(table, nchunks, esize);
+  const float* gscale = gscale_ptr(gstats);
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (esize == 2)
+    hipLaunchKernelGGL((scale_mt_kernel<bf16_t>), dim3((int)nchunks),
+                       dim3(256), 0, stream, table_ptr(table), gscale);
+  else
+    hipLaunchKernelGGL((scale_mt_kernel<float>), dim3((int)nchunks),
+                       dim3(256), 0, stream, table_ptr(table), gscale);
+  HIP_CHECK_LAST();
+}
+
+// the *_table entry points run the update from a prebuilt table; gstats
+// (optional) is the grad-norm stats tensor whose [1] scales every grad
+void fused_adam_table(at::Tensor table, long nchunks, long esize, double lr,
+                      double b1, double b2, double eps, double wd, double bc1,
+                      double bc2, c10::optional<at::Tensor> gstats) {
+  check_table(table, nchunks, esize);
+  const float* gscale = gscale_ptr(gstats);
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const float* no_lr = nullptr;
+  const long long* no_step = nullptr;
+  LAUNCH_UPDATE(adam_mt_kernel, esize, gscale, dim3((int)nchunks), dim3(256),
+                0, stream, table_ptr(table), (float)lr, (float)b1, (float)b2,
+                (float)eps, (float)wd, (float)bc1, (float)bc2, no_lr, no_step,
+                gscale);
+  HIP_CHECK_LAST();
+}
+
+void fused_adam(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
+                std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
+                std::vector<at::Tensor> masters, double lr, double b1,
+                double b2, double eps, double wd, double bc1, double bc2) {
+  if (ps.empty()) return;
+  int nchunks = 0, esize = 4;
+  auto dev_chunks = build_chunks(ps, gs, ms, vs, masters, nchunks, esize);
+  fused_adam_table(dev_chunks, nchunks, esize, lr, b1, b2, eps, wd, bc1, bc2,
+                   c10::nullopt);
+}
+
+// graph-capturable Adam: prebuilt table, lr/step in device buffers
 void fused_adam_graph(at::Tensor table, long nchunks, long esize,
                       at::Tensor lr_buf, double b1, double b2, double eps,
-                      double wd, at::Tensor step_buf) {
+                      double wd, at::Tensor step_buf,
+                      c10::optional<at::Tensor> gstats) {
   TORCH_CHECK(table.is_cuda() && lr_buf.is_cuda() && step_buf.is_cuda());
   TORCH_CHECK(lr_buf.scalar_type() == at::kFloat &&
               step_buf.scalar_type() == at::kLong);
+  const float* gscale = gscale_ptr(gstats);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (esize == 2)
-    hipLaunchKernelGGL((adam_mt_kernel<bf16_t>), dim3((int)nchunks),
-                       dim3(256), 0, stream,
-                       reinterpret_cast<const Chunk*>(table.data_ptr()), 0.f,
-                       (float)b1, (float)b2, (float)eps, (float)wd, 1.f, 1.f,
-                       lr_buf.data_ptr<float>(),
-                       reinterpret_cast<const long long*>(
-                           step_buf.data_ptr<int64_t>()));
-  else
-    hipLaunchKernelGGL((adam_mt_kernel<float>), dim3((int)nchunks),
-                       dim3(256), 0, stream,
-                       reinterpret_cast<const Chunk*>(table.data_ptr()), 0.f,
-                       (float)b1, (float)b2, (float)eps, (float)wd, 1.f, 1.f,
-                       lr_buf.data_ptr<float>(),
-                       reinterpret_cast<const long long*>(
-                           step_buf.data_ptr<int64_t>()));
+  const float* lr_p = lr_buf.data_ptr<float>();
+  const long long* step_p =
+      reinterpret_cast<const long long*>(step_buf.data_ptr<int64_t>());
+  LAUNCH_UPDATE(adam_mt_kernel, esize, gscale, dim3((int)nchunks), dim3(256),
+                0, stream, table_ptr(table), 0.f, (float)b1, (float)b2,
+                (float)eps, (float)wd, 1.f, 1.f, lr_p, step_p, gscale);
+  HIP_CHECK_LAST();
+}
+
+void fused_sgd_table(at::Tensor table, long nchunks, long esize, double lr,
+                     double momentum, double wd, bool nesterov,
+                     c10::optional<at::Tensor> gstats) {
+  check_table(table, nchunks, esize);
+  const float* gscale = gscale_ptr(gstats);
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  LAUNCH_UPDATE(sgd_mt_kernel, esize, gscale, dim3((int)nchunks), dim3(256),
+                0, stream, table_ptr(table), (float)lr, (float)momentum,
+                (float)wd, (int)nesterov, gscale);
   HIP_CHECK_LAST();
 }
 
@@ -344,17 +623,33 @@ void fused_sgd(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
   if (ps.empty()) return;
   int nchunks = 0, esize = 4;
   auto dev_chunks = build_chunks(ps, gs, bufs, {}, masters, nchunks, esize);
+  fused_sgd_table(dev_chunks, nchunks, esize, lr, momentum, wd, nesterov,
+                  c10::nullopt);
+}
+
+void fused_lamb_table(at::Tensor table, long nchunks, long esize,
+                      long ntensors, double lr, double b1, double b2,
+                      double eps, double wd, double bc1, double bc2,
+                      double clamp_trust, c10::optional<at::Tensor> gstats) {
+  check_table(table, nchunks, esize);
+  TORCH_CHECK(ntensors > 0);
+  const float* gscale = gscale_ptr(gstats);
+  auto norms = at::zeros({ntensors, 2}, table.options().dtype(at::kFloat));
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  LAUNCH_UPDATE(lamb_phase1_kernel, esize, gscale, dim3((int)nchunks),
+                dim3(256), 0, stream, table_ptr(table),
+                norms.data_ptr<float>(), (float)b1, (float)b2, (float)eps,
+                (float)wd, (float)bc1, (float)bc2, gscale);
+#define LAMB_PHASE2(T)                                                       \
+  hipLaunchKernelGGL((lamb_phase2_kernel<T>), dim3((int)nchunks), dim3(256), \
+                     0, stream, table_ptr(table), norms.data_ptr<float>(),   \
+                     (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, \
+                     (float)bc1, (float)bc2, (float)clamp_trust)
   if (esize == 2)
-    hipLaunchKernelGGL((sgd_mt_kernel<bf16_t>), dim3(nchunks), dim3(256), 0,
-                       stream,
-                       reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()),
-                       (float)lr, (float)momentum, (float)wd, nesterov);
+    LAMB_PHASE2(bf16_t);
   else
-    hipLaunchKernelGGL((sgd_mt_kernel<float>), dim3(nchunks), dim3(256), 0,
-                       stream,
-                       reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()),
-                       (float)lr, (float)momentum, (float)wd, nesterov);
+    LAMB_PHASE2(float);
+#undef LAMB_PHASE2
   HIP_CHECK_LAST();
 }
 
@@ -366,28 +661,8 @@ void fused_lamb(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
   if (ps.empty()) return;
   int nchunks = 0, esize = 4;
   auto dev_chunks = build_chunks(ps, gs, ms, vs, masters, nchunks, esize);
-  auto norms = at::zeros({(long)ps.size(), 2},
-                         ps[0].options().dtype(at::kFloat));
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-#define LAMB_LAUNCH(T)                                                       \
-  do {                                                                       \
-    hipLaunchKernelGGL((lamb_phase1_kernel<T>), dim3(nchunks), dim3(256), 0, \
-                       stream,                                               \
-                       reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()),\
-                       norms.data_ptr<float>(), (float)b1, (float)b2,        \
-                       (float)eps, (float)wd, (float)bc1, (float)bc2);       \
-    hipLaunchKernelGGL((lamb_phase2_kernel<T>), dim3(nchunks), dim3(256), 0, \
-                       stream,                                               \
-                       reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()),\
-                       norms.data_ptr<float>(), (float)lr, (float)b1,        \
-                       (float)b2, (float)eps, (float)wd, (float)bc1,         \
-                       (float)bc2, (float)clamp_trust);                      \
-  } while (0)
-  if (esize == 2)
-    LAMB_LAUNCH(bf16_t);
-  else
-    LAMB_LAUNCH(float);
-  HIP_CHECK_LAST();
+  fused_lamb_table(dev_chunks, nchunks, esize, (long)ps.size(), lr, b1, b2,
+                   eps, wd, bc1, bc2, clamp_trust, c10::nullopt);
 }
 
 

@@ -50,7 +50,8 @@ class ComputeEngine:
                  criterion=None,
                  loss_filename: str = "losses.txt",
                  amp_dtype: torch.dtype | None = None,
-                 versioning: bool = True):
+                 versioning: bool = True,
+                 max_grad_norm: float | None = None):
         self.model = model
         self.optimizer = optimizer
         self.device = device
@@ -61,6 +62,20 @@ class ComputeEngine:
         # versioning=False (single-fused-stage training) skips the
         # per-step parameter snapshot clones: no recompute ever happens
         self.versioning = versioning
+        # global-norm gradient clipping, once per optimizer step (i.e. on
+        # the ACCUMULATED gradient at the update_frequency boundary). An
+        # optimizer with the fused option (ops.FusedAdam/SGD/LAMB) folds
+        # the coefficient into its update kernel; any other optimizer gets
+        # ops.clip_grad_norm_ right before each step(). Set BEFORE the
+        # graph step is built: a captured optimizer records the clip.
+        self.max_grad_norm = max_grad_norm
+        self._clip_external = False
+        self._last_norm = None
+        if max_grad_norm is not None and optimizer is not None:
+            if hasattr(optimizer, "grad_norm_stats"):
+                optimizer.max_grad_norm = max_grad_norm
+            else:
+                self._clip_external = True
         # hipGraph capture of the fused step (fwd+loss+bwd single
         # launch; see graphstep.py). Only safe when no recompute/grad
         # accumulation semantics are in play.
@@ -89,6 +104,25 @@ class ComputeEngine:
 
         self._params = list(self.model.parameters())
         self._snapshot_current()
+
+    def _optimizer_step(self):
+        if self._clip_external:
+            from ..ops import clip_grad_norm_
+            self._last_norm = clip_grad_norm_(self._params,
+                                              self.max_grad_norm)
+        self.optimizer.step()
+
+    def last_grad_norm(self) -> float | None:
+        """Total gradient norm (before clipping) seen by the most recent
+        optimizer step, as a python float; None when clipping is off or
+        no step has run. Synchronises with the device only when called."""
+        if self.max_grad_norm is None or self.optimizer is None:
+            return None
+        if self._clip_external:
+            return None if self._last_norm is None \
+                else float(self._last_norm)
+        stats = self.optimizer.grad_norm_stats()
+        return None if stats is None else float(stats[0])
 
     def _autocast(self):
         if self.amp_dtype is not None and self.device.type == "cuda":
@@ -272,7 +306,7 @@ class ComputeEngine:
                 self.n_backwards % self.update_frequency == 0:
             if self.pre_step_hook is not None:
                 self.pre_step_hook()
-            self.optimizer.step()
+            self._optimizer_step()
             self.optimizer.zero_grad(set_to_none=True)
             self.model.zero_grad(set_to_none=True)
             self.bump_version()
@@ -328,7 +362,7 @@ class ComputeEngine:
                 self.n_backwards % self.update_frequency == 0:
             if self.pre_step_hook is not None:
                 self.pre_step_hook()
-            self.optimizer.step()
+            self._optimizer_step()
             self.optimizer.zero_grad(set_to_none=True)
             self.model.zero_grad(set_to_none=True)
             self.bump_version()
@@ -356,7 +390,7 @@ class ComputeEngine:
             self.optimizer.bump_host_steps()
             stepped = True
         elif self.optimizer is not None:
-            self.optimizer.step()
+            self._optimizer_step()
             stepped = True
         loss_val = float(loss_t)
         self.file_loss += loss_val

@@ -114,7 +114,8 @@ class Node:
                  wire_dtype: torch.dtype | None = None,
                  amp_dtype: torch.dtype | None = None,
                  async_reduce: bool = True,
-                 model_transform=None):
+                 model_transform=None,
+                 max_grad_norm: float | None = None):
         # parity: the reference's fp16 wire compression (utils.py:184-194)
         # becomes an optional on-the-wire cast; bf16 is the natural MI355X
         # wire dtype (no clamping needed)
@@ -203,7 +204,8 @@ class Node:
                                     criterion=criterion,
                                     loss_filename=loss_filename,
                                     amp_dtype=amp_dtype,
-                                    versioning=not self.fused)
+                                    versioning=not self.fused,
+                                    max_grad_norm=max_grad_norm)
 
         # ---- routing precomputation ---------------------------------
         self._build_routing()

@@ -5,7 +5,7 @@ from .activation import (GELU, LinearGelu, Softmax, gelu, bias_gelu,
 from .dropout import Dropout, dropout
 from .attention import (AttentionCore, AttentionCoreQKV, attention, attention_qkv)
 from .losses import CrossEntropyLoss, cross_entropy
-from .optim import FusedAdam, FusedSGD, FusedLAMB
+from .optim import FusedAdam, FusedSGD, FusedLAMB, clip_grad_norm_
 from .batchnorm import FusedBatchNorm2d
 from .linear import Linear
 from .conv import Conv1x1, conv2d_mfma
@@ -20,7 +20,7 @@ __all__ = [
     "Dropout", "dropout",
     "AttentionCore", "AttentionCoreQKV", "attention", "attention_qkv",
     "CrossEntropyLoss", "cross_entropy",
-    "FusedAdam", "FusedSGD", "FusedLAMB",
+    "FusedAdam", "FusedSGD", "FusedLAMB", "clip_grad_norm_",
     "FusedBatchNorm2d", "Linear", "Conv1x1", "conv2d_mfma",
     "embedding_ln", "embedding_add",
     "MaxPool2d", "AvgPool2d", "AdaptiveAvgPool2d",

@@ -6,8 +6,16 @@ GPU path: ONE kernel launch per step applies the update across every
 parameter chunk (csrc/optim.hip, apex-style chunked multi-tensor apply);
 LAMB adds a norm-reduction phase for the per-tensor trust ratio. CPU
 path: plain torch math (used by the CPU pipeline tests).
+
+Global-norm gradient clipping (``max_grad_norm``): a multi-tensor
+squared-norm reduction writes a device scalar coefficient that the update
+kernels multiply into every gradient AS THEY LOAD IT — one extra read of
+the gradients and no write, no host synchronisation, capturable in a
+hipGraph. The gradients in memory keep their unclipped values.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 from torch.optim import Optimizer
@@ -19,12 +27,117 @@ def _on_gpu(params):
     return any(p.is_cuda for p in params)
 
 
-class FusedAdam(Optimizer):
+def _cpu_clip_stats(grads, max_norm, stats):
+    """torch.nn.utils.clip_grad_norm_'s formula (L2) on the CPU path:
+    fills stats = [norm, coefficient, non-finite count] and returns the
+    coefficient as a python float."""
+    if grads:
+        norm = torch.linalg.vector_norm(torch.stack(
+            [torch.linalg.vector_norm(g.detach().float()) for g in grads]))
+    else:
+        norm = torch.zeros(())
+    coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+    stats[0] = norm
+    stats[1] = coef
+    if not math.isfinite(float(norm)):
+        stats[2] += 1
+    return float(coef)
+
+
+class _GradClipMixin:
+    """``max_grad_norm`` support shared by the fused optimizers.
+
+    The option is a plain attribute (NOT a param-group default): it stays
+    out of ``state_dict`` so old checkpoints load unchanged and the owner
+    (Node / ComputeEngine) re-supplies it on resume. The norm spans every
+    param group of the optimizer.
+    """
+
+    max_grad_norm: float | None = None
+    _clip_stats = None      # [norm, coefficient, non-finite count] fp32
+    _clip_partials = None   # per-chunk partial sums (GPU path)
+
+    def _stats_on(self, device):
+        st = self._clip_stats
+        if st is None or st.device != torch.device(device):
+            old = st
+            st = torch.zeros(3, dtype=torch.float32, device=device)
+            if old is not None:
+                st[2] = float(old[2])
+            self._clip_stats = st
+        return st
+
+    def _partials_on(self, device, n):
+        buf = self._clip_partials
+        if buf is None or buf.device != torch.device(device) \
+                or buf.numel() < n:
+            buf = torch.empty(max(n, 1), dtype=torch.float32, device=device)
+            self._clip_partials = buf
+        return buf
+
+    def grad_norm_stats(self):
+        """Device tensor [norm before clipping, clip coefficient, count of
+        non-finite-norm steps] of the most recent clipped step (None before
+        the first one). Returned without any synchronisation."""
+        return self._clip_stats
+
+    def _clip_tables(self, ext, work):
+        """GPU clip prologue. ``work`` is one (ps, gs, ms, vs, masters)
+        tuple per param group with grads. Uploads ONE chunk table per
+        group (shared by the norm kernel and the update kernel), reduces
+        the squared norm of all groups into one partials buffer and
+        finalizes [norm, coefficient, count]. Returns (tables, stats)."""
+        tables = [ext.mt_build_table(*w) for w in work]
+        total = sum(t[1] for t in tables)
+        device = work[0][0][0].device
+        stats = self._stats_on(device)
+        partials = self._partials_on(device, total)
+        off = 0
+        for table, nchunks, esize in tables:
+            ext.grad_sqnorm(table, nchunks, esize, partials, off)
+            off += nchunks
+        ext.grad_norm_finalize(partials, total, stats,
+                               float(self.max_grad_norm))
+        return tables, stats
+
+    def _masters(self, ps):
+        return ([self.state[p]["master"] for p in ps]
+                if ps[0].dtype == torch.bfloat16 else [])
+
+    def _step_clipped(self):
+        """step() with max_grad_norm set: norm over ALL groups first, then
+        each group's update with the coefficient. The optimizer supplies
+        _collect(group) -> lists (params first, grads second),
+        _table_lists(lists) -> the five build-table lists,
+        _update_from_table(...) and _cpu_update(group, lists, coef)."""
+        work = []
+        for group in self.param_groups:
+            lists = self._collect(group)
+            if lists[0]:
+                work.append((group, lists))
+        if not work:
+            return
+        grads = [g for _, lists in work for g in lists[1]]
+        if _on_gpu(grads):
+            ext = get_ext(required=True)
+            tables, stats = self._clip_tables(
+                ext, [self._table_lists(lists) for _, lists in work])
+            for (group, lists), table in zip(work, tables):
+                self._update_from_table(ext, group, lists, table, stats)
+        else:
+            stats = self._stats_on("cpu")
+            coef = _cpu_clip_stats(grads, float(self.max_grad_norm), stats)
+            for group, lists in work:
+                self._cpu_update(group, lists, coef)
+
+
+class FusedAdam(_GradClipMixin, Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0):
+                 weight_decay=0.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps,
                         weight_decay=weight_decay)
         super().__init__(params, defaults)
+        self.max_grad_norm = max_grad_norm
         self._graph = None  # hipGraph-capture buffers (see graph_step)
 
     # ---- hipGraph capture support (engine/graphstep.py) --------------
@@ -44,7 +157,14 @@ class FusedAdam(Optimizer):
             "step": torch.full((1,), start, dtype=torch.int64,
                                device=device),
             "table": None,
+            # clipping is recorded into the capture only when it is on at
+            # capture time; max_norm then lives in a device scalar that
+            # sync_lr refreshes, like lr
+            "clip": self.max_grad_norm is not None,
+            "max_norm": torch.zeros(1, dtype=torch.float32, device=device),
         }
+        if self._graph["clip"]:
+            self._stats_on(device)
         self.sync_lr()
         return True
 
@@ -60,9 +180,15 @@ class FusedAdam(Optimizer):
                         st["master"] = p.detach().float().clone()
 
     def sync_lr(self):
-        """Host -> device lr refresh; call OUTSIDE the graph, before each
-        replay (lets lr schedules work under capture)."""
+        """Host -> device lr (and max_grad_norm) refresh; call OUTSIDE the
+        graph, before each replay (lets lr schedules work under capture).
+        ``max_grad_norm = None`` after a clipping capture uploads +inf:
+        the recorded kernels then compute a coefficient of exactly 1."""
         self._graph["lr"].fill_(float(self.param_groups[0]["lr"]))
+        if self._graph["clip"]:
+            mn = self.max_grad_norm
+            self._graph["max_norm"].fill_(
+                float("inf") if mn is None else float(mn))
 
     def bump_host_steps(self):
         """Mirror the device step counter into the python state (kept
@@ -95,11 +221,17 @@ class FusedAdam(Optimizer):
         self._graph["table"] = ext.adam_build_table(ps, grads, ms, vs,
                                                     masters)
         self._graph["grads"] = grads
+        if self._graph["clip"]:
+            # preallocated outside the capture: replays reuse the buffer
+            self._graph["partials"] = torch.empty(
+                self._graph["table"][1], dtype=torch.float32,
+                device=ps[0].device)
         return grads
 
     @torch.no_grad()
     def graph_step(self):
-        """The capturable step body: device step bump + ONE kernel.
+        """The capturable step body: device step bump + ONE kernel (with
+        clipping: sqnorm -> finalize -> update, a serial chain).
         Must run inside the captured region, after backward."""
         ext = get_ext(required=True)
         g = self._graph
@@ -107,6 +239,15 @@ class FusedAdam(Optimizer):
         group = self.param_groups[0]
         b1, b2 = group["betas"]
         table, nchunks, esize = g["table"]
+        if g["clip"]:
+            stats = self._clip_stats
+            ext.grad_sqnorm(table, nchunks, esize, g["partials"], 0)
+            ext.grad_norm_finalize(g["partials"], nchunks, stats, 0.0,
+                                   g["max_norm"])
+            ext.fused_adam_graph(table, nchunks, esize, g["lr"], b1, b2,
+                                 group["eps"], group["weight_decay"],
+                                 g["step"], stats)
+            return
         ext.fused_adam_graph(table, nchunks, esize, g["lr"], b1, b2,
                              group["eps"], group["weight_decay"],
                              g["step"])
@@ -114,29 +255,15 @@ class FusedAdam(Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self.max_grad_norm is not None:
+            self._step_clipped()
+            return loss
         for group in self.param_groups:
-            ps, gs, ms, vs = [], [], [], []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["m"] = torch.zeros_like(p, dtype=torch.float32)
-                    st["v"] = torch.zeros_like(p, dtype=torch.float32)
-                    if p.dtype == torch.bfloat16 and p.is_cuda:
-                        st["master"] = p.detach().float().clone()
-                st["step"] += 1
-                ps.append(p)
-                gs.append(p.grad)
-                ms.append(st["m"])
-                vs.append(st["v"])
+            ps, gs, ms, vs = lists = self._collect(group)
             if not ps:
                 continue
             b1, b2 = group["betas"]
-            step = self.state[ps[0]]["step"]
-            bc1 = 1 - b1 ** step
-            bc2 = 1 - b2 ** step
+            bc1, bc2 = self._bias_corrections(group, ps)
             if _on_gpu(ps):
                 ext = get_ext(required=True)
                 masters = ([self.state[p]["master"] for p in ps]
@@ -144,103 +271,209 @@ class FusedAdam(Optimizer):
                 ext.fused_adam(ps, gs, ms, vs, masters, group["lr"], b1, b2,
                                group["eps"], group["weight_decay"], bc1, bc2)
             else:
-                for p, g, m, v in zip(ps, gs, ms, vs):
-                    gf = g.float()
-                    if group["weight_decay"]:
-                        gf = gf.add(p.float(), alpha=group["weight_decay"])
-                    m.mul_(b1).add_(gf, alpha=1 - b1)
-                    v.mul_(b2).addcmul_(gf, gf, value=1 - b2)
-                    denom = (v / bc2).sqrt_().add_(group["eps"])
-                    p.add_(((m / bc1) / denom).to(p.dtype),
-                           alpha=-group["lr"])
+                self._cpu_update(group, lists, None)
         return loss
 
+    def _collect(self, group):
+        ps, gs, ms, vs = [], [], [], []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = 0
+                st["m"] = torch.zeros_like(p, dtype=torch.float32)
+                st["v"] = torch.zeros_like(p, dtype=torch.float32)
+                if p.dtype == torch.bfloat16 and p.is_cuda:
+                    st["master"] = p.detach().float().clone()
+            st["step"] += 1
+            ps.append(p)
+            gs.append(p.grad)
+            ms.append(st["m"])
+            vs.append(st["v"])
+        return ps, gs, ms, vs
 
-class FusedSGD(Optimizer):
+    def _bias_corrections(self, group, ps):
+        b1, b2 = group["betas"]
+        step = self.state[ps[0]]["step"]
+        return 1 - b1 ** step, 1 - b2 ** step
+
+    def _table_lists(self, lists):
+        return (*lists, self._masters(lists[0]))
+
+    def _update_from_table(self, ext, group, lists, table, stats):
+        b1, b2 = group["betas"]
+        bc1, bc2 = self._bias_corrections(group, lists[0])
+        ext.fused_adam_table(*table, group["lr"], b1, b2, group["eps"],
+                             group["weight_decay"], bc1, bc2, stats)
+
+    def _cpu_update(self, group, lists, coef):
+        b1, b2 = group["betas"]
+        bc1, bc2 = self._bias_corrections(group, lists[0])
+        for p, g, m, v in zip(*lists):
+            gf = g.float()
+            if coef is not None:
+                gf = gf * coef
+            if group["weight_decay"]:
+                gf = gf.add(p.float(), alpha=group["weight_decay"])
+            m.mul_(b1).add_(gf, alpha=1 - b1)
+            v.mul_(b2).addcmul_(gf, gf, value=1 - b2)
+            denom = (v / bc2).sqrt_().add_(group["eps"])
+            p.add_(((m / bc1) / denom).to(p.dtype),
+                   alpha=-group["lr"])
+
+
+class FusedSGD(_GradClipMixin, Optimizer):
     def __init__(self, params, lr=1e-2, momentum=0.0, weight_decay=0.0,
-                 nesterov=False):
+                 nesterov=False, max_grad_norm=None):
         defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
                         nesterov=nesterov)
         super().__init__(params, defaults)
+        self.max_grad_norm = max_grad_norm
+
+    def _collect(self, group):
+        ps, gs, bufs = [], [], []
+        mom = group["momentum"]
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            st = self.state[p]
+            if mom and "momentum_buffer" not in st:
+                st["momentum_buffer"] = torch.zeros_like(
+                    p, dtype=torch.float32)
+            if p.dtype == torch.bfloat16 and p.is_cuda and \
+                    "master" not in st:
+                st["master"] = p.detach().float().clone()
+            ps.append(p)
+            gs.append(p.grad)
+            bufs.append(st["momentum_buffer"] if mom
+                        else torch.zeros(0))
+        return ps, gs, bufs
+
+    def _table_lists(self, lists):
+        ps, gs, bufs = lists
+        return ps, gs, bufs, [], self._masters(ps)
+
+    def _update_from_table(self, ext, group, lists, table, stats):
+        ext.fused_sgd_table(*table, group["lr"], group["momentum"],
+                            group["weight_decay"], bool(group["nesterov"]),
+                            stats)
+
+    def _cpu_update(self, group, lists, coef):
+        mom = group["momentum"]
+        for p, g, b in zip(*lists):
+            gf = g.float()
+            if coef is not None:
+                gf = gf * coef
+            if group["weight_decay"]:
+                gf = gf.add(p.float(), alpha=group["weight_decay"])
+            if mom:
+                b.mul_(mom).add_(gf)
+                gf = gf.add(b, alpha=mom) if group["nesterov"] else b
+            p.add_(gf.to(p.dtype), alpha=-group["lr"])
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self.max_grad_norm is not None:
+            self._step_clipped()
+            return loss
         for group in self.param_groups:
-            ps, gs, bufs = [], [], []
-            mom = group["momentum"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if mom and "momentum_buffer" not in st:
-                    st["momentum_buffer"] = torch.zeros_like(
-                        p, dtype=torch.float32)
-                if p.dtype == torch.bfloat16 and p.is_cuda and \
-                        "master" not in st:
-                    st["master"] = p.detach().float().clone()
-                ps.append(p)
-                gs.append(p.grad)
-                bufs.append(st["momentum_buffer"] if mom
-                            else torch.zeros(0))
+            ps, gs, bufs = lists = self._collect(group)
             if not ps:
                 continue
             if _on_gpu(ps):
                 ext = get_ext(required=True)
                 masters = ([self.state[p]["master"] for p in ps]
                            if ps[0].dtype == torch.bfloat16 else [])
-                ext.fused_sgd(ps, gs, bufs, masters, group["lr"], mom,
-                              group["weight_decay"],
+                ext.fused_sgd(ps, gs, bufs, masters, group["lr"],
+                              group["momentum"], group["weight_decay"],
                               bool(group["nesterov"]))
             else:
-                for p, g, b in zip(ps, gs, bufs):
-                    gf = g.float()
-                    if group["weight_decay"]:
-                        gf = gf.add(p.float(), alpha=group["weight_decay"])
-                    if mom:
-                        b.mul_(mom).add_(gf)
-                        gf = gf.add(b, alpha=mom) if group["nesterov"] else b
-                    p.add_(gf.to(p.dtype), alpha=-group["lr"])
+                self._cpu_update(group, lists, None)
         return loss
 
 
-class FusedLAMB(Optimizer):
+class FusedLAMB(_GradClipMixin, Optimizer):
     """LAMB (You et al.) with the per-tensor trust ratio
     clamp(|w| / |update|). Parity: torch_optimizer.Lamb used by the BERT
     example (examples/bert/provider.py:49-50)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
-                 weight_decay=0.0, clamp_trust=10.0):
+                 weight_decay=0.0, clamp_trust=10.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps,
                         weight_decay=weight_decay, clamp_trust=clamp_trust)
         super().__init__(params, defaults)
+        self.max_grad_norm = max_grad_norm
+
+    def _collect(self, group):
+        ps, gs, ms, vs = [], [], [], []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = 0
+                st["m"] = torch.zeros_like(p, dtype=torch.float32)
+                st["v"] = torch.zeros_like(p, dtype=torch.float32)
+                if p.dtype == torch.bfloat16 and p.is_cuda:
+                    st["master"] = p.detach().float().clone()
+            st["step"] += 1
+            ps.append(p)
+            gs.append(p.grad)
+            ms.append(st["m"])
+            vs.append(st["v"])
+        return ps, gs, ms, vs
+
+    def _bias_corrections(self, group, ps):
+        b1, b2 = group["betas"]
+        step = self.state[ps[0]]["step"]
+        return 1 - b1 ** step, 1 - b2 ** step
+
+    def _table_lists(self, lists):
+        return (*lists, self._masters(lists[0]))
+
+    def _update_from_table(self, ext, group, lists, table, stats):
+        b1, b2 = group["betas"]
+        bc1, bc2 = self._bias_corrections(group, lists[0])
+        table, nchunks, esize = table
+        ext.fused_lamb_table(table, nchunks, esize, len(lists[0]),
+                             group["lr"], b1, b2, group["eps"],
+                             group["weight_decay"], bc1, bc2,
+                             group["clamp_trust"], stats)
+
+    def _cpu_update(self, group, lists, coef):
+        b1, b2 = group["betas"]
+        bc1, bc2 = self._bias_corrections(group, lists[0])
+        for p, g, m, v in zip(*lists):
+            gf = g.float()
+            if coef is not None:
+                gf = gf * coef
+            m.mul_(b1).add_(gf, alpha=1 - b1)
+            v.mul_(b2).addcmul_(gf, gf, value=1 - b2)
+            upd = (m / bc1) / ((v / bc2).sqrt() + group["eps"])
+            if group["weight_decay"]:
+                upd = upd.add(p.float(), alpha=group["weight_decay"])
+            wn = p.float().norm()
+            un = upd.norm()
+            trust = torch.where(
+                (wn > 0) & (un > 0),
+                (wn / un).clamp(max=group["clamp_trust"]),
+                torch.ones_like(wn))
+            p.add_((trust * upd).to(p.dtype), alpha=-group["lr"])
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self.max_grad_norm is not None:
+            self._step_clipped()
+            return loss
         for group in self.param_groups:
             b1, b2 = group["betas"]
-            ps, gs, ms, vs = [], [], [], []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["m"] = torch.zeros_like(p, dtype=torch.float32)
-                    st["v"] = torch.zeros_like(p, dtype=torch.float32)
-                    if p.dtype == torch.bfloat16 and p.is_cuda:
-                        st["master"] = p.detach().float().clone()
-                st["step"] += 1
-                ps.append(p)
-                gs.append(p.grad)
-                ms.append(st["m"])
-                vs.append(st["v"])
+            ps, gs, ms, vs = lists = self._collect(group)
             if not ps:
                 continue
-            step = self.state[ps[0]]["step"]
-            bc1 = 1 - b1 ** step
-            bc2 = 1 - b2 ** step
+            bc1, bc2 = self._bias_corrections(group, ps)
             if _on_gpu(ps):
                 ext = get_ext(required=True)
                 masters = ([self.state[p]["master"] for p in ps]
@@ -249,18 +482,50 @@ class FusedLAMB(Optimizer):
                                group["eps"], group["weight_decay"], bc1, bc2,
                                group["clamp_trust"])
             else:
-                for p, g, m, v in zip(ps, gs, ms, vs):
-                    gf = g.float()
-                    m.mul_(b1).add_(gf, alpha=1 - b1)
-                    v.mul_(b2).addcmul_(gf, gf, value=1 - b2)
-                    upd = (m / bc1) / ((v / bc2).sqrt() + group["eps"])
-                    if group["weight_decay"]:
-                        upd = upd.add(p.float(), alpha=group["weight_decay"])
-                    wn = p.float().norm()
-                    un = upd.norm()
-                    trust = torch.where(
-                        (wn > 0) & (un > 0),
-                        (wn / un).clamp(max=group["clamp_trust"]),
-                        torch.ones_like(wn))
-                    p.add_((trust * upd).to(p.dtype), alpha=-group["lr"])
+                self._cpu_update(group, lists, None)
         return loss
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm) -> torch.Tensor:
+    """Drop-in for ``torch.nn.utils.clip_grad_norm_`` (L2 norm), for use
+    with any optimizer. Scales the gradients in place by
+    ``min(1, max_norm / (norm + 1e-6))`` and returns the 0-dim total norm
+    (a device tensor on GPU: no synchronisation). Params without a grad
+    are skipped; with no grads at all the result is 0.
+
+    GPU: grads are grouped by dtype (bf16 and fp32 may be mixed); one
+    squared-norm launch per dtype fills one partials buffer, one finalize
+    launch produces the coefficient, one scale launch per dtype applies
+    it. A non-finite norm behaves as torch with error_if_nonfinite=False.
+    """
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    if not _on_gpu(grads):
+        return torch.nn.utils.clip_grad_norm_(
+            [p for p in parameters if p.grad is not None], max_norm)
+    ext = get_ext(required=True)
+    by_dtype: dict = {}
+    for g in grads:
+        if g.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError(
+                f"clip_grad_norm_: unsupported grad dtype {g.dtype} "
+                "(bf16 and fp32 only)")
+        by_dtype.setdefault(g.dtype, []).append(g)
+    device = grads[0].device
+    tables = [t for t in (ext.grad_build_table(gs)
+                          for gs in by_dtype.values()) if t[1] > 0]
+    total = sum(t[1] for t in tables)
+    stats = torch.zeros(3, dtype=torch.float32, device=device)
+    partials = torch.empty(max(total, 1), dtype=torch.float32, device=device)
+    off = 0
+    for table, nchunks, esize in tables:
+        ext.grad_sqnorm(table, nchunks, esize, partials, off)
+        off += nchunks
+    ext.grad_norm_finalize(partials, total, stats, float(max_norm))
+    for table, nchunks, esize in tables:
+        ext.scale_mt(table, nchunks, esize, stats)
+    return stats[0]
