@@ -61,6 +61,14 @@ std::vector<at::Tensor> emb2_bwd(at::Tensor dx, at::Tensor ids, long V,
 std::vector<at::Tensor> dropout_fwd(at::Tensor x, double p, int64_t seed,
                                     c10::optional<at::Tensor> seed_buf);
 at::Tensor dropout_bwd(at::Tensor dy, at::Tensor mask, double p);
+std::vector<at::Tensor> dropout_add_ln_fwd(at::Tensor z, at::Tensor a,
+                                           at::Tensor w, at::Tensor bias,
+                                           double eps, double p, int64_t seed,
+                                           c10::optional<at::Tensor> seed_buf);
+std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
+                                           at::Tensor w, at::Tensor mean,
+                                           at::Tensor rstd,
+                                           at::Tensor maskbits, double p);
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets,
                                int64_t ignore_index);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
@@ -138,6 +146,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("p"), py::arg("seed"),
         py::arg("seed_buf") = py::none());
   m.def("dropout_bwd", &dropout_bwd, "dropout bwd");
+  m.def("dropout_add_ln_fwd", &dropout_add_ln_fwd,
+        "fused dropout + residual add + LayerNorm fwd (bf16, bit mask)",
+        py::arg("z"), py::arg("a"), py::arg("w"), py::arg("bias"),
+        py::arg("eps"), py::arg("p"), py::arg("seed"),
+        py::arg("seed_buf") = py::none());
+  m.def("dropout_add_ln_bwd", &dropout_add_ln_bwd,
+        "fused dropout + residual add + LayerNorm bwd: dx, dz, dw, db");
   m.def("conv2d_fwd", &conv2d_fwd,
         "implicit-GEMM MFMA conv fwd (bf16 NCHW)", py::arg("x"),
         py::arg("w"), py::arg("bias") = py::none(), py::arg("st") = 1,

@@ -15,8 +15,8 @@ import torch
 import torch.nn as nn
 
 from ..ops import embedding_ln
-from ..ops import (AddLayerNorm, AttentionCoreQKV, Dropout, FusedLayerNorm,
-                   GELU, LinearGelu)
+from ..ops import (AttentionCoreQKV, Dropout, DropoutAddLayerNorm,
+                   FusedLayerNorm, GELU, LinearGelu)
 from ..ops.linear import make_linear
 
 
@@ -74,8 +74,9 @@ class BertEmbeddings(nn.Module):
 
 class BertSelfAttention(nn.Module):
     """DOCUMENTED SEMANTICS DIFFERENCE vs HuggingFace BERT: by default
-    dropout is applied AFTER the output projection (self.drop below)
-    instead of on the attention probabilities — the fused flash kernel
+    dropout is applied AFTER the output projection (inside BertLayer.ln1,
+    fused with the residual add and the LayerNorm; this module returns the
+    un-dropped projection) instead of on the attention probabilities — the fused flash kernel
     never materializes the S x S probs. Set RAVNEST_EXACT_ATTN_DROPOUT=1
     (before model construction) for exact HF prob-dropout semantics via
     the composed P-materializing path (replayable philox mask; lower
@@ -91,7 +92,6 @@ class BertSelfAttention(nn.Module):
         self.core = AttentionCoreQKV(
             causal=False, prob_dropout=cfg.dropout if exact else 0.0)
         self.out = make_linear(cfg.hidden, cfg.hidden)
-        self.drop = Dropout(cfg.dropout)
 
     def forward(self, x, mask):
         # packed (B,S,3,H,D) qkv: the attention kernel reads the
@@ -100,22 +100,25 @@ class BertSelfAttention(nn.Module):
         # free of .size() scalar nodes)
         qkv = self.qkv(x).unflatten(-1, (3, self.heads, self.head_dim))
         o = self.core(qkv, mask)
-        return self.drop(self.out(o))
+        return self.out(o)
 
 
 class BertLayer(nn.Module):
     def __init__(self, cfg: BertConfig):
         super().__init__()
         self.attn = BertSelfAttention(cfg)
-        self.ln1 = AddLayerNorm(cfg.hidden, cfg.layer_norm_eps)
+        # ln1/ln2 = LN(x + dropout(sublayer)): dropout, residual add and
+        # LayerNorm in one kernel each way (ops/dropout_ln.py)
+        self.ln1 = DropoutAddLayerNorm(cfg.hidden, cfg.layer_norm_eps,
+                                       cfg.dropout)
         self.mlp_in = LinearGelu(cfg.hidden, cfg.intermediate)
         self.mlp_out = make_linear(cfg.intermediate, cfg.hidden)
-        self.drop = Dropout(cfg.dropout)
-        self.ln2 = AddLayerNorm(cfg.hidden, cfg.layer_norm_eps)
+        self.ln2 = DropoutAddLayerNorm(cfg.hidden, cfg.layer_norm_eps,
+                                       cfg.dropout)
 
     def forward(self, x, mask):
         x = self.ln1(x, self.attn(x, mask))
-        x = self.ln2(x, self.drop(self.mlp_out(self.mlp_in(x))))
+        x = self.ln2(x, self.mlp_out(self.mlp_in(x)))
         return x
 
 

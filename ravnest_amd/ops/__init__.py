@@ -3,6 +3,7 @@ from .layernorm import (FusedLayerNorm, AddLayerNorm, layer_norm, add_layer_norm
 from .activation import (GELU, LinearGelu, Softmax, gelu, bias_gelu,
                          softmax)
 from .dropout import Dropout, dropout
+from .dropout_ln import DropoutAddLayerNorm, dropout_add_layer_norm
 from .attention import (AttentionCore, AttentionCoreQKV, attention, attention_qkv)
 from .losses import CrossEntropyLoss, cross_entropy
 from .optim import FusedAdam, FusedSGD, FusedLAMB, clip_grad_norm_
@@ -18,6 +19,7 @@ __all__ = [
     "FusedLayerNorm", "AddLayerNorm", "layer_norm", "add_layer_norm",
     "GELU", "LinearGelu", "Softmax", "gelu", "bias_gelu", "softmax",
     "Dropout", "dropout",
+    "DropoutAddLayerNorm", "dropout_add_layer_norm",
     "AttentionCore", "AttentionCoreQKV", "attention", "attention_qkv",
     "CrossEntropyLoss", "cross_entropy",
     "FusedAdam", "FusedSGD", "FusedLAMB", "clip_grad_norm_",
