@@ -73,6 +73,13 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets,
                                int64_t ignore_index);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
                   at::Tensor gscale, int64_t ignore_index);
+std::vector<at::Tensor> mlm_head_fwd(at::Tensor h, at::Tensor W,
+                                     at::Tensor b, at::Tensor targets,
+                                     int64_t ignore_index);
+std::vector<at::Tensor> mlm_head_bwd(at::Tensor dloss, at::Tensor logits_c,
+                                     at::Tensor lse, at::Tensor hc,
+                                     at::Tensor tc, at::Tensor pos,
+                                     at::Tensor count, at::Tensor W);
 std::tuple<at::Tensor, long, long> adam_build_table(
     std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
     std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
@@ -188,6 +195,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "embedding bwd: dword scatter-add + dpos batch reduction");
   m.def("ce_fwd", &ce_fwd, "fused softmax cross-entropy fwd");
   m.def("ce_bwd", &ce_bwd, "fused softmax cross-entropy bwd");
+  m.def("mlm_head_fwd", &mlm_head_fwd,
+        "sparse MLM head fwd: decoder GEMM + CE on the non-ignored rows "
+        "(device-side live count, graph-capturable)");
+  m.def("mlm_head_bwd", &mlm_head_bwd,
+        "sparse MLM head bwd: dh, dW, db (consumes the saved logits)");
   m.def("fused_adam", &fused_adam, "multi-tensor Adam");
   m.def("adam_build_table", &adam_build_table,
         "prebuild the device chunk table (graph-capturable Adam)");

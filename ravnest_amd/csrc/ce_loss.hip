@@ -30,20 +30,11 @@ DEVINL void ms_merge(float& m, float& s, float m2, float s2) {
   m = mn;
 }
 
+// log-sum-exp of one row of V values, computed by the whole block
+// (result returned to every thread)
 template <typename T>
-__global__ void ce_fwd_kernel(const T* __restrict__ logits,
-                              const long* __restrict__ targets,
-                              float* __restrict__ lse_out,
-                              float* __restrict__ loss_accum,
-                              int* __restrict__ valid_accum, int V, long N,
-                              long ignore_index) {
-  __shared__ float scratch_m[16];
-  __shared__ float scratch_s[16];
-  const long row = blockIdx.x;
-  if (row >= N) return;
-  const T* lr = logits + row * V;
-  const long tgt = targets[row];
-
+DEVINL float row_lse(const T* __restrict__ lr, int V, float* scratch_m,
+                     float* scratch_s) {
   float m = -INFINITY, s = 0.f;
   if constexpr (sizeof(T) == 2) {
     // vectorized: 8 bf16 per thread per iteration (16B loads)
@@ -121,7 +112,24 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
     m = scratch_m[0];
     s = scratch_s[0];
   }
-  const float lse = m + __logf(s);
+  return m + __logf(s);
+}
+
+template <typename T>
+__global__ void ce_fwd_kernel(const T* __restrict__ logits,
+                              const long* __restrict__ targets,
+                              float* __restrict__ lse_out,
+                              float* __restrict__ loss_accum,
+                              int* __restrict__ valid_accum, int V, long N,
+                              long ignore_index) {
+  __shared__ float scratch_m[16];
+  __shared__ float scratch_s[16];
+  const long row = blockIdx.x;
+  if (row >= N) return;
+  const T* lr = logits + row * V;
+  const long tgt = targets[row];
+
+  const float lse = row_lse(lr, V, scratch_m, scratch_s);
 
   if (threadIdx.x == 0) {
     lse_out[row] = lse;
@@ -177,6 +185,68 @@ __global__ void ce_bwd_kernel(const T* __restrict__ logits,
       float p = __expf(ld(lr + i) - l);
       dr[i] = (p - (i == (int)tgt ? 1.f : 0.f)) * g;
     }
+  }
+}
+
+// ---- live-row variants (sparse MLM head, csrc/mlm_head.hip) -----------
+// The logits buffer holds only the rows whose label is not ignored,
+// compacted to the front: [cap][ld] bf16 with ld >= V (ld % 8 == 0). The
+// number of live rows is a DEVICE int (it changes per replay of a
+// captured graph): the grid covers cap rows and a block past the count
+// returns at once. No ignore test: every row below the count is live.
+__global__ void ce_rows_fwd_kernel(const bf16_t* __restrict__ logits,
+                                   const long* __restrict__ tc,
+                                   const int* __restrict__ count,
+                                   float* __restrict__ lse_out,
+                                   float* __restrict__ loss_accum, int V,
+                                   long ld) {
+  __shared__ float scratch_m[16];
+  __shared__ float scratch_s[16];
+  const long row = blockIdx.x;
+  if (row >= *count) return;  // uniform per block, before any barrier
+  const bf16_t* lr = logits + row * ld;
+  const float lse = row_lse(lr, V, scratch_m, scratch_s);
+  if (threadIdx.x == 0) {
+    lse_out[row] = lse;
+    atomicAdd(loss_accum, lse - bf2f(lr[tc[row]]));
+  }
+}
+
+// in place: logits row -> (softmax - onehot) * dloss / max(count, 1).
+// Also zeroes the pad columns [V, ld) of live rows and the whole pad rows
+// [count, round_up(count, 64)), so the GEMMs that reduce over either
+// dimension in 64-wide tiles read zeros, never stale values.
+__global__ void ce_rows_bwd_kernel(bf16_t* __restrict__ logits,
+                                   const long* __restrict__ tc,
+                                   const int* __restrict__ count,
+                                   const float* __restrict__ lse,
+                                   const float* __restrict__ dloss, int V,
+                                   long ld) {
+  const long row = blockIdx.x;
+  const int cnt = *count;
+  if (row >= (((long)cnt + 63) & ~63l)) return;
+  bf16_t* dr = logits + row * ld;
+  const int nld = (int)(ld >> 3);
+  if (row >= cnt) {
+    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int gi = threadIdx.x; gi < nld; gi += blockDim.x)
+      *reinterpret_cast<bf16x8*>(dr + gi * 8) = z;
+    return;
+  }
+  const int tgt = (int)tc[row];
+  const float g = dloss[0] / (float)max(cnt, 1);
+  const float l = lse[row];
+  for (int gi = threadIdx.x; gi < nld; gi += blockDim.x) {
+    const bf16x8 v8 = *reinterpret_cast<const bf16x8*>(dr + gi * 8);
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = gi * 8 + j;
+      const float p = __expf(us2f((unsigned short)v8[j]) - l);
+      const float d = (p - (i == tgt ? 1.f : 0.f)) * g;
+      o[j] = i < V ? (short)f2us(d) : (short)0;
+    }
+    *reinterpret_cast<bf16x8*>(dr + gi * 8) = o;
   }
 }
 
@@ -236,4 +306,49 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
   }
   HIP_CHECK_LAST();
   return dlogits;
+}
+
+// live-row CE forward over the compact logits [cap, ld]; returns
+// {loss_sum (fp32 scalar), lse[cap]} (lse rows past the count are unset)
+std::vector<at::Tensor> ce_rows_fwd(at::Tensor logits, at::Tensor tc,
+                                    at::Tensor count, int64_t V) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() &&
+              logits.dim() == 2 && logits.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(tc.scalar_type() == at::kLong && tc.is_contiguous() &&
+              tc.numel() >= logits.size(0));
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.numel() == 1);
+  const long cap = logits.size(0), ld = logits.size(1);
+  TORCH_CHECK(ld % 8 == 0 && V <= ld && V >= 1);
+  auto lse = at::empty({cap}, logits.options().dtype(at::kFloat));
+  auto loss = at::zeros({1}, logits.options().dtype(at::kFloat));
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  hipLaunchKernelGGL(ce_rows_fwd_kernel, dim3(cap), dim3(256), 0, stream,
+                     reinterpret_cast<const bf16_t*>(logits.data_ptr()),
+                     tc.data_ptr<long>(), count.data_ptr<int>(),
+                     lse.data_ptr<float>(), loss.data_ptr<float>(), (int)V,
+                     ld);
+  HIP_CHECK_LAST();
+  return {loss.squeeze(0), lse};
+}
+
+// live-row CE backward, IN PLACE on the logits buffer (see the kernel)
+void ce_rows_bwd_(at::Tensor logits, at::Tensor tc, at::Tensor count,
+                  at::Tensor lse, at::Tensor dloss, int64_t V) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() &&
+              logits.dim() == 2 && logits.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(tc.scalar_type() == at::kLong && tc.is_contiguous());
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.numel() == 1);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.numel() >= logits.size(0));
+  TORCH_CHECK(dloss.scalar_type() == at::kFloat && dloss.numel() == 1 &&
+              dloss.is_cuda());
+  const long cap = logits.size(0), ld = logits.size(1);
+  TORCH_CHECK(ld % 8 == 0 && V <= ld && cap % 64 == 0);
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  hipLaunchKernelGGL(ce_rows_bwd_kernel, dim3(cap), dim3(256), 0, stream,
+                     reinterpret_cast<bf16_t*>(logits.data_ptr()),
+                     tc.data_ptr<long>(), count.data_ptr<int>(),
+                     lse.data_ptr<float>(), dloss.data_ptr<float>(), (int)V,
+                     ld);
+  HIP_CHECK_LAST();
 }

@@ -104,10 +104,22 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
     const bf16_t* __restrict__ bias, bf16_t* __restrict__ C,
     bf16_t* __restrict__ H, long M, long N, long K, int MT, int NTb,
-    int tpb) {
+    int tpb, long ldc, const int* __restrict__ mlimit) {
   __shared__ char smem[2 * BUF_BYTES];
 
+  // optional device-side row limit (the live-row count of a compacted
+  // operand, unknown to the host inside a captured graph): it replaces M
+  // everywhere below. The grid stays sized for the host M; the row-tile
+  // count is recomputed so the XCD remap spreads the LIVE tiles over the
+  // chip, and surplus blocks leave here — uniform per block, before any
+  // barrier or staging.
+  if (mlimit != nullptr) {
+    const long lim = *mlimit;
+    if (lim < M) M = lim < 0 ? 0 : lim;
+    MT = (int)((M + BM - 1) / BM);
+  }
   const int nwg = MT * NTb;
+  if ((int)blockIdx.x >= nwg) return;
   int bid = blockIdx.x, wg;
   if ((nwg & 7) == 0) {
     wg = (bid & 7) * (nwg >> 3) + (bid >> 3);
@@ -335,20 +347,20 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(
         if (EPI == 2) {
           u16x4 h{f2us(v0), f2us(v1), f2us(v2), f2us(v3)};
           if (full) {
-            *reinterpret_cast<u16x4*>(H + m * N + n) = h;
+            *reinterpret_cast<u16x4*>(H + m * ldc + n) = h;
           } else {
             for (int v = 0; v < 4; ++v)
-              if (n + v < N) H[m * N + n + v] = f2bf(us2f(h[v]));
+              if (n + v < N) H[m * ldc + n + v] = f2bf(us2f(h[v]));
           }
           v0 = gelu_f(v0); v1 = gelu_f(v1);
           v2 = gelu_f(v2); v3 = gelu_f(v3);
         }
         const u16x4 o{f2us(v0), f2us(v1), f2us(v2), f2us(v3)};
         if (full) {
-          *reinterpret_cast<u16x4*>(C + m * N + n) = o;
+          *reinterpret_cast<u16x4*>(C + m * ldc + n) = o;
         } else {
           for (int v = 0; v < 4; ++v)
-            if (n + v < N) C[m * N + n + v] = f2bf(us2f(o[v]));
+            if (n + v < N) C[m * ldc + n + v] = f2bf(us2f(o[v]));
         }
       }
     }
@@ -363,9 +375,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(
 
 }  // namespace
 
-std::vector<at::Tensor> gemm_nt_bf16(at::Tensor A2, at::Tensor B,
-                                     c10::optional<at::Tensor> bias,
-                                     int64_t epi) {
+// shape checks + launch shared by the two host entry points. `ldc` is the
+// row stride of C (and H) in elements; `mlimit` (device int, may be null)
+// caps the rows computed — see the kernel.
+static void launch_gemm_nt(const at::Tensor& A2, const at::Tensor& B,
+                           const c10::optional<at::Tensor>& bias,
+                           int64_t epi, bf16_t* c, bf16_t* hp, long ldc,
+                           const int* mlimit) {
   TORCH_CHECK(A2.is_cuda() && A2.scalar_type() == at::kBFloat16 &&
               A2.is_contiguous() && A2.dim() == 2);
   TORCH_CHECK(B.is_cuda() && B.scalar_type() == at::kBFloat16 &&
@@ -378,24 +394,25 @@ std::vector<at::Tensor> gemm_nt_bf16(at::Tensor A2, at::Tensor B,
               "gemm_nt_bf16: operands must be < 4 GiB (32-bit staging "
               "offsets)");
   TORCH_CHECK(epi == 0 || bias.has_value(), "bias required for epi>=1");
+  TORCH_CHECK(ldc == N || (ldc > N && ldc % 4 == 0),
+              "gemm_nt_bf16: ldc must cover N (and keep 8-byte stores "
+              "aligned when padded)");
   const bf16_t* bp = nullptr;
   if (bias.has_value()) {
     TORCH_CHECK(bias->is_contiguous() &&
                 bias->scalar_type() == at::kBFloat16 && bias->numel() == N);
     bp = reinterpret_cast<const bf16_t*>(bias->data_ptr());
   }
-  auto C = at::empty({M, N}, A2.options());
-  at::Tensor Hp;
-  bf16_t* hp = nullptr;
-  if (epi == 2) {
-    Hp = at::empty({M, N}, A2.options());
-    hp = reinterpret_cast<bf16_t*>(Hp.data_ptr());
-  }
   const int MT = (int)((M + BM - 1) / BM), NT = (int)((N + BN - 1) / BN);
   // column tiles per block: amortizes the per-block staging cold start;
   // capped so the grid still fills the chip (>= ~2 block-waves)
   int tpb = 1;
   for (int cand : {8, 6, 4, 3, 2}) {
+    // under a device row limit only a fraction of the row tiles is live,
+    // unknown here: shorter blocks keep the last block-wave's idle tail
+    // small (15 % of 65536 rows x 30522: 585 blocks of 8 tiles = 2.3
+    // block-waves -> 3 rounds; 1170 blocks of 4 tiles = 4.6 -> 5 rounds)
+    if (mlimit != nullptr && cand > 4) continue;
     if (NT % cand == 0 && (long)MT * (NT / cand) >= 512) {
       tpb = cand;
       break;
@@ -406,21 +423,53 @@ std::vector<at::Tensor> gemm_nt_bf16(at::Tensor A2, at::Tensor B,
   dim3 grid((unsigned)(MT * NTb)), block(512);
   auto* a = reinterpret_cast<const bf16_t*>(A2.data_ptr());
   auto* b = reinterpret_cast<const bf16_t*>(B.data_ptr());
-  auto* c = reinterpret_cast<bf16_t*>(C.data_ptr());
   switch (epi) {
     case 0:
       hipLaunchKernelGGL((gemm_nt_kernel<0>), grid, block, 0, stream, a, b,
-                         bp, c, hp, M, N, K, MT, NTb, tpb);
+                         bp, c, hp, M, N, K, MT, NTb, tpb, ldc, mlimit);
       break;
     case 1:
       hipLaunchKernelGGL((gemm_nt_kernel<1>), grid, block, 0, stream, a, b,
-                         bp, c, hp, M, N, K, MT, NTb, tpb);
+                         bp, c, hp, M, N, K, MT, NTb, tpb, ldc, mlimit);
       break;
     default:
       hipLaunchKernelGGL((gemm_nt_kernel<2>), grid, block, 0, stream, a, b,
-                         bp, c, hp, M, N, K, MT, NTb, tpb);
+                         bp, c, hp, M, N, K, MT, NTb, tpb, ldc, mlimit);
   }
   HIP_CHECK_LAST();
+}
+
+std::vector<at::Tensor> gemm_nt_bf16(at::Tensor A2, at::Tensor B,
+                                     c10::optional<at::Tensor> bias,
+                                     int64_t epi) {
+  TORCH_CHECK(A2.dim() == 2 && B.dim() == 2);
+  const long M = A2.size(0), N = B.size(0);
+  auto C = at::empty({M, N}, A2.options());
+  at::Tensor Hp;
+  bf16_t* hp = nullptr;
+  if (epi == 2) {
+    Hp = at::empty({M, N}, A2.options());
+    hp = reinterpret_cast<bf16_t*>(Hp.data_ptr());
+  }
+  launch_gemm_nt(A2, B, bias, epi, reinterpret_cast<bf16_t*>(C.data_ptr()),
+                 hp, N, nullptr);
   if (epi == 2) return {C, Hp};
   return {C};
+}
+
+// C[0:rows, 0:N] = A2[0:rows] @ B^T (+bias), rows = min(A2.size(0),
+// *row_limit) read ON DEVICE, written into the caller's buffer `C` whose
+// row stride is C.size(1) >= N. Rows at or past the limit and the pad
+// columns [N, C.size(1)) are left untouched. epi in {0, 1}.
+void gemm_nt_bf16_rows(at::Tensor A2, at::Tensor B,
+                       c10::optional<at::Tensor> bias, int64_t epi,
+                       at::Tensor C, at::Tensor row_limit) {
+  TORCH_CHECK(epi == 0 || epi == 1, "gemm_nt_bf16_rows: epi 0 or 1");
+  TORCH_CHECK(C.is_cuda() && C.scalar_type() == at::kBFloat16 &&
+              C.is_contiguous() && C.dim() == 2 &&
+              C.size(0) >= A2.size(0) && C.size(1) >= B.size(0));
+  TORCH_CHECK(row_limit.is_cuda() && row_limit.scalar_type() == at::kInt &&
+              row_limit.numel() == 1);
+  launch_gemm_nt(A2, B, bias, epi, reinterpret_cast<bf16_t*>(C.data_ptr()),
+                 nullptr, C.size(1), row_limit.data_ptr<int>());
 }

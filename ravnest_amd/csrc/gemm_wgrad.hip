@@ -59,7 +59,7 @@ template <bool TAIL>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(
     const bf16_t* __restrict__ DY, const bf16_t* __restrict__ X,
     float* __restrict__ WS, long M, long N, long K, int NT, int KT,
-    int splitk, long mTilesPer) {
+    int splitk, long mTilesPer, const int* __restrict__ mbound) {
   __shared__ char smem[2 * PAIR_BYTES];
 
   // block -> (output tile, m-slice); slices of one tile stay adjacent
@@ -78,8 +78,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(
   const long n0 = (long)bn * BN, k0 = (long)bk * BK;
   const bool is_tail = (n0 + BN > N) || (k0 + BK > K);
   if (TAIL != is_tail) return;  // the two specializations split the grid
+  // optional device-side bound on the reduction (live rows of a
+  // compacted operand): the m-tiles below round_up(*mbound, 64) are
+  // re-split evenly over the slices; slices left empty exit. The caller
+  // keeps rows [*mbound, round_up) zero in dy and finite in x.
+  long mTiles = M / BM;
+  if (mbound != nullptr) {
+    const long bt = ((long)max(*mbound, 0) + BM - 1) / BM;
+    if (bt < mTiles) mTiles = bt;
+    mTilesPer = (mTiles + splitk - 1) / splitk;
+  }
   const long mt0 = slice * mTilesPer;
-  const long mt1 = min(mt0 + mTilesPer, M / BM);
+  const long mt1 = min(mt0 + mTilesPer, mTiles);
   if (mt0 >= mt1) return;
 
   const int tid = threadIdx.x;
@@ -259,7 +269,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(
 
 }  // namespace
 
-at::Tensor gemm_wgrad_bf16(at::Tensor dy, at::Tensor x) {
+static at::Tensor launch_wgrad(const at::Tensor& dy, const at::Tensor& x,
+                               const int* mbound) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16 &&
               dy.is_contiguous() && dy.dim() == 2);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
@@ -285,13 +296,26 @@ at::Tensor gemm_wgrad_bf16(at::Tensor dy, at::Tensor x) {
                      reinterpret_cast<const bf16_t*>(dy.data_ptr()),
                      reinterpret_cast<const bf16_t*>(x.data_ptr()),
                      ws.data_ptr<float>(), M, N, K, NT, KT, splitk,
-                     mTilesPer);
+                     mTilesPer, mbound);
   if (has_tail)
     hipLaunchKernelGGL((wgrad_kernel<true>), grid, block, 0, stream,
                        reinterpret_cast<const bf16_t*>(dy.data_ptr()),
                        reinterpret_cast<const bf16_t*>(x.data_ptr()),
                        ws.data_ptr<float>(), M, N, K, NT, KT, splitk,
-                       mTilesPer);
+                       mTilesPer, mbound);
   HIP_CHECK_LAST();
   return ws;
+}
+
+at::Tensor gemm_wgrad_bf16(at::Tensor dy, at::Tensor x) {
+  return launch_wgrad(dy, x, nullptr);
+}
+
+// dW = dy[0:R]^T @ x[0:R] with R = round_up(min(*row_bound, M), 64) read
+// ON DEVICE (a captured graph cannot size the grid by it).
+at::Tensor gemm_wgrad_bf16_rows(at::Tensor dy, at::Tensor x,
+                                at::Tensor row_bound) {
+  TORCH_CHECK(row_bound.is_cuda() && row_bound.scalar_type() == at::kInt &&
+              row_bound.numel() == 1);
+  return launch_wgrad(dy, x, row_bound.data_ptr<int>());
 }

@@ -30,6 +30,7 @@ from dataclasses import dataclass
 import torch
 
 from ..utils import current_rng_states, restore_rng_states, trace_range
+from .fused_loss import model_loss
 
 
 @dataclass
@@ -342,8 +343,8 @@ class ComputeEngine:
                 a = a.detach().clone().requires_grad_(True)
             live_args.append(a)
         with self._autocast():
-            out = self.model(*live_args)
-            loss = self.criterion(out, targets)
+            loss = model_loss(self.model, self.criterion, live_args,
+                              targets)
         loss.backward()
         loss_val = float(loss.detach())
         self.file_loss += loss_val

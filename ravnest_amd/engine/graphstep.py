@@ -29,6 +29,7 @@ from __future__ import annotations
 import torch
 
 from ..ops import rng
+from .fused_loss import model_loss
 
 
 def _sig(tensors):
@@ -118,8 +119,8 @@ class GraphedTrainStep:
             if with_opt:
                 # stable (non-pool) grad buffers: zero, accumulate, apply
                 torch._foreach_zero_(stable_grads)
-            out = self.model(*s_args)
-            loss = self.criterion(out, s_tgts[0])
+            loss = model_loss(self.model, self.criterion, s_args,
+                              s_tgts[0])
             loss.backward()
             if with_opt:
                 self.optimizer.graph_step()

@@ -130,8 +130,12 @@ class BertMLMHead(nn.Module):
         self.ln = FusedLayerNorm(cfg.hidden, cfg.layer_norm_eps)
         self.decoder = make_linear(cfg.hidden, cfg.vocab_size)
 
+    def transform(self, x):
+        """dense -> GELU -> LayerNorm: the decoder's input."""
+        return self.ln(self.act(self.dense(x)))
+
     def forward(self, x):
-        return self.decoder(self.ln(self.act(self.dense(x))))
+        return self.decoder(self.transform(x))
 
 
 class BertForMLM(nn.Module):
@@ -156,11 +160,40 @@ class BertForMLM(nn.Module):
         elif isinstance(m, nn.Embedding):
             nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, input_ids, attention_mask):
+    def _encode(self, input_ids, attention_mask):
         # additive mask: (B,S) {0,1} -> (B,1,1,S) {0,-inf-ish}
         m = (1.0 - attention_mask.to(torch.float32)) * -10000.0
         m = m.unsqueeze(1).unsqueeze(2)
         x = self.embeddings(input_ids)
         for layer in self.layers:
             x = layer(x, m)
-        return self.head(x)
+        return x
+
+    def forward(self, input_ids, attention_mask):
+        return self.head(self._encode(input_ids, attention_mask))
+
+    def forward_loss(self, input_ids, attention_mask, targets, criterion):
+        """Opt-in fused model+criterion step: encoder and head transform
+        as in forward(), then decoder + cross-entropy on the rows whose
+        label is not ignored only (ops/mlm_head.py). Returns the loss, or
+        None when the fused op does not apply — the caller then computes
+        criterion(self(input_ids, attention_mask), targets)."""
+        from ..ops.losses import CrossEntropyLoss
+        from ..ops.mlm_head import (sparse_mlm_head_enabled,
+                                    sparse_mlm_head_loss,
+                                    sparse_mlm_head_supported)
+        dec = self.head.decoder
+        if not (self.training and sparse_mlm_head_enabled()
+                and type(criterion) is CrossEntropyLoss
+                and torch.is_tensor(targets) and input_ids.is_cuda
+                and dec.weight.is_cuda
+                and dec.weight.dtype == torch.bfloat16
+                and not torch.is_autocast_enabled()
+                and targets.numel() == input_ids.numel()):
+            return None
+        if not sparse_mlm_head_supported(dec.weight, dec.bias, targets):
+            return None
+        x = self._encode(input_ids, attention_mask)
+        h = self.head.transform(x)
+        return sparse_mlm_head_loss(h, dec.weight, dec.bias, targets,
+                                    criterion.ignore_index)

@@ -6,6 +6,7 @@ from .dropout import Dropout, dropout
 from .dropout_ln import DropoutAddLayerNorm, dropout_add_layer_norm
 from .attention import (AttentionCore, AttentionCoreQKV, attention, attention_qkv)
 from .losses import CrossEntropyLoss, cross_entropy
+from .mlm_head import sparse_mlm_head_loss
 from .optim import FusedAdam, FusedSGD, FusedLAMB, clip_grad_norm_
 from .batchnorm import FusedBatchNorm2d
 from .linear import Linear
@@ -21,7 +22,7 @@ __all__ = [
     "Dropout", "dropout",
     "DropoutAddLayerNorm", "dropout_add_layer_norm",
     "AttentionCore", "AttentionCoreQKV", "attention", "attention_qkv",
-    "CrossEntropyLoss", "cross_entropy",
+    "CrossEntropyLoss", "cross_entropy", "sparse_mlm_head_loss",
     "FusedAdam", "FusedSGD", "FusedLAMB", "clip_grad_norm_",
     "FusedBatchNorm2d", "Linear", "Conv1x1", "conv2d_mfma",
     "embedding_ln", "embedding_add",
