@@ -80,7 +80,7 @@ std::vector<at::Tensor> mlm_head_bwd(at::Tensor dloss, at::Tensor logits_c,
                                      at::Tensor lse, at::Tensor hc,
                                      at::Tensor tc, at::Tensor pos,
                                      at::Tensor count, at::Tensor W);
-std::tuple<at::Tensor, long, long> adam_build_table(
+std::tuple<at::Tensor, long, long> mt_build_table(
     std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
     std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
     std::vector<at::Tensor> masters);
@@ -106,18 +106,6 @@ void fused_lamb_table(at::Tensor table, long nchunks, long esize,
                       long ntensors, double lr, double b1, double b2,
                       double eps, double wd, double bc1, double bc2,
                       double clamp_trust, c10::optional<at::Tensor> gstats);
-void fused_adam(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-                std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
-                std::vector<at::Tensor> masters, double lr, double b1,
-                double b2, double eps, double wd, double bc1, double bc2);
-void fused_sgd(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-               std::vector<at::Tensor> bufs, std::vector<at::Tensor> masters,
-               double lr, double momentum, double wd, bool nesterov);
-void fused_lamb(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-                std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
-                std::vector<at::Tensor> masters, double lr, double b1,
-                double b2, double eps, double wd, double bc1, double bc2,
-                double clamp_trust);
 void fused_copy(std::vector<at::Tensor> srcs, std::vector<at::Tensor> dsts);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor mask, bool causal, double scale);
@@ -200,15 +188,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(device-side live count, graph-capturable)");
   m.def("mlm_head_bwd", &mlm_head_bwd,
         "sparse MLM head bwd: dh, dW, db (consumes the saved logits)");
-  m.def("fused_adam", &fused_adam, "multi-tensor Adam");
-  m.def("adam_build_table", &adam_build_table,
-        "prebuild the device chunk table (graph-capturable Adam)");
   m.def("fused_adam_graph", &fused_adam_graph,
         "multi-tensor Adam with device lr/step buffers (hipGraph mode)",
         py::arg("table"), py::arg("nchunks"), py::arg("esize"),
         py::arg("lr_buf"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
         py::arg("wd"), py::arg("step_buf"), py::arg("gstats") = py::none());
-  m.def("mt_build_table", &adam_build_table,
+  m.def("mt_build_table", &mt_build_table,
         "prebuild the device chunk table (any fused optimizer)");
   m.def("grad_build_table", &grad_build_table,
         "grads-only device chunk table (clip_grad_norm_)");
@@ -236,8 +221,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ntensors"), py::arg("lr"), py::arg("b1"), py::arg("b2"),
         py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2"),
         py::arg("clamp_trust"), py::arg("gstats") = py::none());
-  m.def("fused_sgd", &fused_sgd, "multi-tensor SGD+momentum");
-  m.def("fused_lamb", &fused_lamb, "multi-tensor LAMB");
   m.def("fused_copy", &fused_copy, "multi-tensor device copy");
   m.def("attn_fwd", &attn_fwd, "flash attention fwd (bf16, MFMA)");
   m.def("attn_bwd", &attn_bwd, "flash attention bwd (bf16, MFMA, D=64)");

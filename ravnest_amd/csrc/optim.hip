@@ -333,89 +333,69 @@ __global__ void scale_mt_kernel(const Chunk* __restrict__ chunks,
     stv<T>(c.g, i, ldv<T>(c.g, i) * gs);
 }
 
-// build the device-side chunk table; returns element dtype size (2|4)
-at::Tensor build_chunks(const std::vector<at::Tensor>& ps,
-                        const std::vector<at::Tensor>& gs,
-                        const std::vector<at::Tensor>& ms,
-                        const std::vector<at::Tensor>& vs,
-                        const std::vector<at::Tensor>& masters, int& nchunks,
-                        int& esize) {
-  std::vector<Chunk> chunks;
-  esize = ps[0].scalar_type() == at::kBFloat16 ? 2 : 4;
-  for (size_t t = 0; t < ps.size(); ++t) {
-    // any DENSE layout is fine (channels_last conv weights included):
-    // the update is elementwise over raw storage, so p/g/state only need
-    // to share one layout
-    const bool dense =
-        ps[t].is_contiguous() ||
-        ps[t].is_contiguous(at::MemoryFormat::ChannelsLast) ||
-        ps[t].is_contiguous(at::MemoryFormat::ChannelsLast3d);
-    TORCH_CHECK(dense, "fused optimizer: param must be dense");
-    TORCH_CHECK(gs[t].strides() == ps[t].strides(),
-                "grad layout must match param layout");
-    TORCH_CHECK(gs[t].scalar_type() == ps[t].scalar_type(),
-                "grad dtype must match param dtype");
-    long n = ps[t].numel();
-    void* p = ps[t].data_ptr();
-    void* g = gs[t].data_ptr();
-    float* m = (ms.empty() || ms[t].numel() == 0)
-                   ? nullptr : ms[t].data_ptr<float>();
-    float* v = (vs.empty() || vs[t].numel() == 0)
-                   ? nullptr : vs[t].data_ptr<float>();
-    float* master = masters.empty() ? nullptr
-                                    : masters[t].data_ptr<float>();
-    const int es = ps[t].scalar_type() == at::kBFloat16 ? 2 : 4;
-    TORCH_CHECK(es == esize, "mixed param dtypes in one group");
-    TORCH_CHECK(es == 4 || master != nullptr,
-                "bf16 params require fp32 masters");
-    for (long off = 0; off < n; off += CHUNK) {
-      Chunk c;
-      c.p = (char*)p + off * es;
-      c.g = (char*)g + off * es;
-      c.m = m ? m + off : nullptr;
-      c.v = v ? v + off : nullptr;
-      c.master = master ? master + off : nullptr;
-      c.n = (int)std::min<long>(CHUNK, n - off);
-      c.tensor_idx = (int)t;
-      chunks.push_back(c);
-    }
-  }
-  nchunks = (int)chunks.size();
-  auto host = at::from_blob(chunks.data(),
-                            {(long)(chunks.size() * sizeof(Chunk))},
-                            at::TensorOptions().dtype(at::kByte));
-  return host.to(ps[0].device());  // blocking copy: host buffer dies here
-}
+// one record per chunk of fused_copy: tensors of 2- and 4-byte elements
+// may share a launch, so the element size travels with the chunk
+struct CopyRec {
+  const void* src;
+  void* dst;
+  int n;      // elements in this chunk
+  int esize;  // 2 or 4
+};
 
 // multi-tensor device copy: ONE launch clones every parameter into its
 // snapshot slot (the versioning engine's per-step param snapshot was ~200
 // separate hipMemcpy calls — SURVEY.md section 2.3 "multi-tensor
-// clone/copy kernels ... versioned weight arena").
-__global__ void copy_mt_kernel(const Chunk* __restrict__ chunks) {
-  const Chunk c = chunks[blockIdx.x];
-  // p = src, m = dst (fp32 elems) OR 2-byte mode via tensor_idx flag
-  if (c.tensor_idx == 2) {  // 2-byte elements
+// clone/copy kernels ... versioned weight arena"). Per chunk a 16-byte
+// vector body, which assumes 16-byte aligned tensor bases, then a scalar
+// tail.
+__global__ void copy_mt_kernel(const CopyRec* __restrict__ recs) {
+  const CopyRec c = recs[blockIdx.x];
+  if (c.esize == 2) {
     const int n4 = c.n >> 3;  // 16B groups of 8 bf16
-    const ulong2* src = reinterpret_cast<const ulong2*>(c.p);
-    ulong2* dst = reinterpret_cast<ulong2*>(c.g);
+    const ulong2* src = reinterpret_cast<const ulong2*>(c.src);
+    ulong2* dst = reinterpret_cast<ulong2*>(c.dst);
     for (int i = threadIdx.x; i < n4; i += blockDim.x) dst[i] = src[i];
     for (int i = (n4 << 3) + threadIdx.x; i < c.n; i += blockDim.x)
-      reinterpret_cast<bf16_t*>(c.g)[i] =
-          reinterpret_cast<const bf16_t*>(c.p)[i];
+      reinterpret_cast<bf16_t*>(c.dst)[i] =
+          reinterpret_cast<const bf16_t*>(c.src)[i];
   } else {
     const int n4 = c.n >> 2;
-    const float4* src = reinterpret_cast<const float4*>(c.p);
-    float4* dst = reinterpret_cast<float4*>(c.g);
+    const float4* src = reinterpret_cast<const float4*>(c.src);
+    float4* dst = reinterpret_cast<float4*>(c.dst);
     for (int i = threadIdx.x; i < n4; i += blockDim.x) dst[i] = src[i];
     for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += blockDim.x)
-      reinterpret_cast<float*>(c.g)[i] =
-          reinterpret_cast<const float*>(c.p)[i];
+      reinterpret_cast<float*>(c.dst)[i] =
+          reinterpret_cast<const float*>(c.src)[i];
   }
 }
 
-}  // namespace
+// ---- host side ---------------------------------------------------------
+// emit(offset, count) for every CHUNK-sized piece of an n-element tensor
+template <typename F>
+void for_each_chunk(long n, F&& emit) {
+  for (long off = 0; off < n; off += CHUNK)
+    emit(off, (int)std::min<long>(CHUNK, n - off));
+}
 
-namespace {
+// chunk records -> device byte tensor. The copy blocks, so the host vector
+// may die when this returns; no records give an empty tensor.
+template <typename Rec>
+at::Tensor upload(const std::vector<Rec>& recs, const at::Device& device) {
+  const auto bytes = at::TensorOptions().dtype(at::kByte);
+  if (recs.empty()) return at::empty({0}, bytes.device(device));
+  return at::from_blob(const_cast<Rec*>(recs.data()),
+                       {(long)(recs.size() * sizeof(Rec))}, bytes)
+      .to(device);
+}
+
+// one 256-thread block per chunk record, on the current stream
+template <typename... Params, typename... Args>
+void launch_mt(void (*kernel)(Params...), long nblocks, Args... args) {
+  hipLaunchKernelGGL(
+      kernel, dim3((int)nblocks), dim3(256), 0,
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(), args...);
+  HIP_CHECK_LAST();
+}
 
 inline const Chunk* table_ptr(const at::Tensor& table) {
   return reinterpret_cast<const Chunk*>(table.data_ptr());
@@ -431,20 +411,6 @@ inline const float* gscale_ptr(const c10::optional<at::Tensor>& gstats) {
   return s.data_ptr<float>() + 1;
 }
 
-// pick the <dtype, clip> instantiation of an update kernel: esize selects
-// bf16/fp32, a non-null gscale selects the clipping variant
-#define LAUNCH_UPDATE(KERNEL, esize, gscale, ...)                            \
-  do {                                                                       \
-    if ((esize) == 2 && (gscale))                                            \
-      hipLaunchKernelGGL((KERNEL<bf16_t, true>), __VA_ARGS__);               \
-    else if ((esize) == 2)                                                   \
-      hipLaunchKernelGGL((KERNEL<bf16_t, false>), __VA_ARGS__);              \
-    else if (gscale)                                                         \
-      hipLaunchKernelGGL((KERNEL<float, true>), __VA_ARGS__);                \
-    else                                                                     \
-      hipLaunchKernelGGL((KERNEL<float, false>), __VA_ARGS__);               \
-  } while (0)
-
 inline void check_table(const at::Tensor& table, long nchunks, long esize) {
   TORCH_CHECK(table.is_cuda() && nchunks > 0 &&
                   table.numel() == nchunks * (long)sizeof(Chunk),
@@ -452,24 +418,98 @@ inline void check_table(const at::Tensor& table, long nchunks, long esize) {
   TORCH_CHECK(esize == 2 || esize == 4, "esize must be 2 or 4");
 }
 
+// the one dtype x clip dispatch: calls f(Elem<T>{}, bool_constant<CLIP>{})
+// with T picked by esize (2 = bf16, 4 = fp32). Kernel families without a
+// CLIP parameter pass clip = false and ignore the second argument.
+template <typename T>
+struct Elem {
+  using type = T;
+};
+
+template <typename F>
+void dispatch(long esize, bool clip, F&& f) {
+  if (esize == 2 && clip)
+    f(Elem<bf16_t>{}, std::true_type{});
+  else if (esize == 2)
+    f(Elem<bf16_t>{}, std::false_type{});
+  else if (clip)
+    f(Elem<float>{}, std::true_type{});
+  else
+    f(Elem<float>{}, std::false_type{});
+}
+
+// the Adam launch behind fused_adam_table (host lr / bias corrections,
+// null lr_buf and step_buf) and fused_adam_graph (device lr and step)
+void launch_adam(const at::Tensor& table, long nchunks, long esize, float lr,
+                 float b1, float b2, float eps, float wd, float bc1,
+                 float bc2, const float* lr_buf, const long long* step_buf,
+                 const c10::optional<at::Tensor>& gstats) {
+  check_table(table, nchunks, esize);
+  const float* gscale = gscale_ptr(gstats);
+  dispatch(esize, gscale != nullptr, [&](auto elem, auto clip) {
+    using T = typename decltype(elem)::type;
+    launch_mt(adam_mt_kernel<T, decltype(clip)::value>, nchunks,
+              table_ptr(table), lr, b1, b2, eps, wd, bc1, bc2, lr_buf,
+              step_buf, gscale);
+  });
+}
+
 }  // namespace
 
 // prebuilt chunk table: ONE blocking upload that several launches of the
-// same step can share (norm reduction + update), or that a captured step
+// same step share (norm reduction + update), or that a captured step
 // reuses across replays (pointers are stable inside a captured step:
 // params/state outside the graph pool, grads at fixed pool addresses).
-std::tuple<at::Tensor, long, long> adam_build_table(
+// Returns (table, nchunks, element size 2|4).
+std::tuple<at::Tensor, long, long> mt_build_table(
     std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
     std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
     std::vector<at::Tensor> masters) {
   TORCH_CHECK(!ps.empty());
-  int nchunks = 0, esize = 4;
-  auto table = build_chunks(ps, gs, ms, vs, masters, nchunks, esize);
-  return {table, (long)nchunks, (long)esize};
+  std::vector<Chunk> chunks;
+  const int esize = ps[0].scalar_type() == at::kBFloat16 ? 2 : 4;
+  for (size_t t = 0; t < ps.size(); ++t) {
+    // any DENSE layout is fine (channels_last conv weights included):
+    // the update is elementwise over raw storage, so p/g/state only need
+    // to share one layout
+    const bool dense =
+        ps[t].is_contiguous() ||
+        ps[t].is_contiguous(at::MemoryFormat::ChannelsLast) ||
+        ps[t].is_contiguous(at::MemoryFormat::ChannelsLast3d);
+    TORCH_CHECK(dense, "fused optimizer: param must be dense");
+    TORCH_CHECK(gs[t].strides() == ps[t].strides(),
+                "grad layout must match param layout");
+    TORCH_CHECK(gs[t].scalar_type() == ps[t].scalar_type(),
+                "grad dtype must match param dtype");
+    char* p = (char*)ps[t].data_ptr();
+    char* g = (char*)gs[t].data_ptr();
+    float* m = (ms.empty() || ms[t].numel() == 0)
+                   ? nullptr : ms[t].data_ptr<float>();
+    float* v = (vs.empty() || vs[t].numel() == 0)
+                   ? nullptr : vs[t].data_ptr<float>();
+    float* master = masters.empty() ? nullptr
+                                    : masters[t].data_ptr<float>();
+    const int es = ps[t].scalar_type() == at::kBFloat16 ? 2 : 4;
+    TORCH_CHECK(es == esize, "mixed param dtypes in one group");
+    TORCH_CHECK(es == 4 || master != nullptr,
+                "bf16 params require fp32 masters");
+    for_each_chunk(ps[t].numel(), [&](long off, int n) {
+      chunks.push_back({p + off * es, g + off * es, m ? m + off : nullptr,
+                        v ? v + off : nullptr,
+                        master ? master + off : nullptr, n, (int)t});
+    });
+  }
+  // release the tensor handles before the blocking upload, not after it:
+  // their refcount decrements then overlap the wait for the stream instead
+  // of standing between the upload and the launch that follows it
+  const at::Device device = ps[0].device();
+  for (auto* list : {&ps, &gs, &ms, &vs, &masters}) list->clear();
+  return {upload(chunks, device), (long)chunks.size(), (long)esize};
 }
 
 // grads-only chunk table (standalone clip_grad_norm_): any dense grads of
-// ONE dtype, including views at unaligned offsets
+// ONE dtype, including views at unaligned offsets. Only zero-element grads
+// give an empty table with nchunks == 0.
 std::tuple<at::Tensor, long, long> grad_build_table(
     std::vector<at::Tensor> gs) {
   TORCH_CHECK(!gs.empty());
@@ -484,22 +524,13 @@ std::tuple<at::Tensor, long, long> grad_build_table(
     TORCH_CHECK(gs[t].scalar_type() == dt, "mixed dtypes in one table");
     TORCH_CHECK(gs[t].is_non_overlapping_and_dense(),
                 "clip_grad_norm_: grad must be dense");
-    const long n = gs[t].numel();
     char* g = (char*)gs[t].data_ptr();
-    for (long off = 0; off < n; off += CHUNK) {
-      Chunk c{};
-      c.p = c.g = g + off * es;
-      c.n = (int)std::min<long>(CHUNK, n - off);
-      c.tensor_idx = (int)t;
-      chunks.push_back(c);
-    }
+    for_each_chunk(gs[t].numel(), [&](long off, int n) {
+      chunks.push_back({g + off * es, g + off * es, nullptr, nullptr,
+                        nullptr, n, (int)t});
+    });
   }
-  if (chunks.empty())  // only zero-element grads
-    return {at::empty({0}, gs[0].options().dtype(at::kByte)), 0L, (long)es};
-  auto host = at::from_blob(chunks.data(),
-                            {(long)(chunks.size() * sizeof(Chunk))},
-                            at::TensorOptions().dtype(at::kByte));
-  return {host.to(gs[0].device()), (long)chunks.size(), (long)es};
+  return {upload(chunks, gs[0].device()), (long)chunks.size(), (long)es};
 }
 
 // partials[offset + i] = sum of squares of chunk i's grads
@@ -510,15 +541,11 @@ void grad_sqnorm(at::Tensor table, long nchunks, long esize,
               partials.is_contiguous());
   TORCH_CHECK(offset >= 0 && offset + nchunks <= partials.numel(),
               "partials buffer too small");
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   float* out = partials.data_ptr<float>() + offset;
-  if (esize == 2)
-    hipLaunchKernelGGL((grad_sqnorm_mt_kernel<bf16_t>), dim3((int)nchunks),
-                       dim3(256), 0, stream, table_ptr(table), out);
-  else
-    hipLaunchKernelGGL((grad_sqnorm_mt_kernel<float>), dim3((int)nchunks),
-                       dim3(256), 0, stream, table_ptr(table), out);
-  HIP_CHECK_LAST();
+  dispatch(esize, false, [&](auto elem, auto) {
+    using T = typename decltype(elem)::type;
+    launch_mt(grad_sqnorm_mt_kernel<T>, nchunks, table_ptr(table), out);
+  });
 }
 
 // stats = [norm, clip coefficient, running non-finite count]; max_norm is
@@ -537,25 +564,18 @@ void grad_norm_finalize(at::Tensor partials, long n, at::Tensor stats,
                 max_norm_buf->numel() >= 1);
     mn = max_norm_buf->data_ptr<float>();
   }
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, stream,
-                     partials.data_ptr<float>(), (int)n, mn, (float)max_norm,
-                     stats.data_ptr<float>());
-  HIP_CHECK_LAST();
+  launch_mt(grad_norm_finalize_kernel, 1, partials.data_ptr<float>(), (int)n,
+            mn, (float)max_norm, stats.data_ptr<float>());
 }
 
 // in-place g *= stats[1] over a grads-only (or full) chunk table
 void scale_mt(at::Tensor table, long nchunks, long esize, at::Tensor gstats) {
   check_table(table, nchunks, esize);
   const float* gscale = gscale_ptr(gstats);
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (esize == 2)
-    hipLaunchKernelGGL((scale_mt_kernel<bf16_t>), dim3((int)nchunks),
-                       dim3(256), 0, stream, table_ptr(table), gscale);
-  else
-    hipLaunchKernelGGL((scale_mt_kernel<float>), dim3((int)nchunks),
-                       dim3(256), 0, stream, table_ptr(table), gscale);
-  HIP_CHECK_LAST();
+  dispatch(esize, false, [&](auto elem, auto) {
+    using T = typename decltype(elem)::type;
+    launch_mt(scale_mt_kernel<T>, nchunks, table_ptr(table), gscale);
+  });
 }
 
 // the *_table entry points run the update from a prebuilt table; gstats
@@ -563,30 +583,13 @@ void scale_mt(at::Tensor table, long nchunks, long esize, at::Tensor gstats) {
 void fused_adam_table(at::Tensor table, long nchunks, long esize, double lr,
                       double b1, double b2, double eps, double wd, double bc1,
                       double bc2, c10::optional<at::Tensor> gstats) {
-  check_table(table, nchunks, esize);
-  const float* gscale = gscale_ptr(gstats);
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const float* no_lr = nullptr;
-  const long long* no_step = nullptr;
-  LAUNCH_UPDATE(adam_mt_kernel, esize, gscale, dim3((int)nchunks), dim3(256),
-                0, stream, table_ptr(table), (float)lr, (float)b1, (float)b2,
-                (float)eps, (float)wd, (float)bc1, (float)bc2, no_lr, no_step,
-                gscale);
-  HIP_CHECK_LAST();
+  launch_adam(table, nchunks, esize, (float)lr, (float)b1, (float)b2,
+              (float)eps, (float)wd, (float)bc1, (float)bc2, nullptr, nullptr,
+              gstats);
 }
 
-void fused_adam(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-                std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
-                std::vector<at::Tensor> masters, double lr, double b1,
-                double b2, double eps, double wd, double bc1, double bc2) {
-  if (ps.empty()) return;
-  int nchunks = 0, esize = 4;
-  auto dev_chunks = build_chunks(ps, gs, ms, vs, masters, nchunks, esize);
-  fused_adam_table(dev_chunks, nchunks, esize, lr, b1, b2, eps, wd, bc1, bc2,
-                   c10::nullopt);
-}
-
-// graph-capturable Adam: prebuilt table, lr/step in device buffers
+// graph-capturable Adam: lr and step in device buffers, so that replays
+// see live values; the kernel derives the bias corrections from step
 void fused_adam_graph(at::Tensor table, long nchunks, long esize,
                       at::Tensor lr_buf, double b1, double b2, double eps,
                       double wd, at::Tensor step_buf,
@@ -594,15 +597,10 @@ void fused_adam_graph(at::Tensor table, long nchunks, long esize,
   TORCH_CHECK(table.is_cuda() && lr_buf.is_cuda() && step_buf.is_cuda());
   TORCH_CHECK(lr_buf.scalar_type() == at::kFloat &&
               step_buf.scalar_type() == at::kLong);
-  const float* gscale = gscale_ptr(gstats);
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const float* lr_p = lr_buf.data_ptr<float>();
-  const long long* step_p =
-      reinterpret_cast<const long long*>(step_buf.data_ptr<int64_t>());
-  LAUNCH_UPDATE(adam_mt_kernel, esize, gscale, dim3((int)nchunks), dim3(256),
-                0, stream, table_ptr(table), 0.f, (float)b1, (float)b2,
-                (float)eps, (float)wd, 1.f, 1.f, lr_p, step_p, gscale);
-  HIP_CHECK_LAST();
+  launch_adam(table, nchunks, esize, 0.f, (float)b1, (float)b2, (float)eps,
+              (float)wd, 1.f, 1.f, lr_buf.data_ptr<float>(),
+              reinterpret_cast<const long long*>(step_buf.data_ptr<int64_t>()),
+              gstats);
 }
 
 void fused_sgd_table(at::Tensor table, long nchunks, long esize, double lr,
@@ -610,21 +608,12 @@ void fused_sgd_table(at::Tensor table, long nchunks, long esize, double lr,
                      c10::optional<at::Tensor> gstats) {
   check_table(table, nchunks, esize);
   const float* gscale = gscale_ptr(gstats);
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  LAUNCH_UPDATE(sgd_mt_kernel, esize, gscale, dim3((int)nchunks), dim3(256),
-                0, stream, table_ptr(table), (float)lr, (float)momentum,
-                (float)wd, (int)nesterov, gscale);
-  HIP_CHECK_LAST();
-}
-
-void fused_sgd(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-               std::vector<at::Tensor> bufs, std::vector<at::Tensor> masters,
-               double lr, double momentum, double wd, bool nesterov) {
-  if (ps.empty()) return;
-  int nchunks = 0, esize = 4;
-  auto dev_chunks = build_chunks(ps, gs, bufs, {}, masters, nchunks, esize);
-  fused_sgd_table(dev_chunks, nchunks, esize, lr, momentum, wd, nesterov,
-                  c10::nullopt);
+  dispatch(esize, gscale != nullptr, [&](auto elem, auto clip) {
+    using T = typename decltype(elem)::type;
+    launch_mt(sgd_mt_kernel<T, decltype(clip)::value>, nchunks,
+              table_ptr(table), (float)lr, (float)momentum, (float)wd,
+              (int)nesterov, gscale);
+  });
 }
 
 void fused_lamb_table(at::Tensor table, long nchunks, long esize,
@@ -635,65 +624,36 @@ void fused_lamb_table(at::Tensor table, long nchunks, long esize,
   TORCH_CHECK(ntensors > 0);
   const float* gscale = gscale_ptr(gstats);
   auto norms = at::zeros({ntensors, 2}, table.options().dtype(at::kFloat));
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  LAUNCH_UPDATE(lamb_phase1_kernel, esize, gscale, dim3((int)nchunks),
-                dim3(256), 0, stream, table_ptr(table),
-                norms.data_ptr<float>(), (float)b1, (float)b2, (float)eps,
-                (float)wd, (float)bc1, (float)bc2, gscale);
-#define LAMB_PHASE2(T)                                                       \
-  hipLaunchKernelGGL((lamb_phase2_kernel<T>), dim3((int)nchunks), dim3(256), \
-                     0, stream, table_ptr(table), norms.data_ptr<float>(),   \
-                     (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, \
-                     (float)bc1, (float)bc2, (float)clamp_trust)
-  if (esize == 2)
-    LAMB_PHASE2(bf16_t);
-  else
-    LAMB_PHASE2(float);
-#undef LAMB_PHASE2
-  HIP_CHECK_LAST();
+  dispatch(esize, gscale != nullptr, [&](auto elem, auto clip) {
+    using T = typename decltype(elem)::type;
+    launch_mt(lamb_phase1_kernel<T, decltype(clip)::value>, nchunks,
+              table_ptr(table), norms.data_ptr<float>(), (float)b1, (float)b2,
+              (float)eps, (float)wd, (float)bc1, (float)bc2, gscale);
+    launch_mt(lamb_phase2_kernel<T>, nchunks, table_ptr(table),
+              norms.data_ptr<float>(), (float)lr, (float)b1, (float)b2,
+              (float)eps, (float)wd, (float)bc1, (float)bc2,
+              (float)clamp_trust);
+  });
 }
 
-void fused_lamb(std::vector<at::Tensor> ps, std::vector<at::Tensor> gs,
-                std::vector<at::Tensor> ms, std::vector<at::Tensor> vs,
-                std::vector<at::Tensor> masters, double lr, double b1,
-                double b2, double eps, double wd, double bc1, double bc2,
-                double clamp_trust) {
-  if (ps.empty()) return;
-  int nchunks = 0, esize = 4;
-  auto dev_chunks = build_chunks(ps, gs, ms, vs, masters, nchunks, esize);
-  fused_lamb_table(dev_chunks, nchunks, esize, (long)ps.size(), lr, b1, b2,
-                   eps, wd, bc1, bc2, clamp_trust, c10::nullopt);
-}
-
-
+// one launch for all tensors; 2- and 4-byte element types may be mixed
 void fused_copy(std::vector<at::Tensor> srcs, std::vector<at::Tensor> dsts) {
-  if (srcs.empty()) return;
-  std::vector<Chunk> chunks;
+  TORCH_CHECK(srcs.size() == dsts.size(), "fused_copy: list lengths differ");
+  std::vector<CopyRec> recs;
   for (size_t t = 0; t < srcs.size(); ++t) {
     TORCH_CHECK(srcs[t].strides() == dsts[t].strides(),
                 "fused_copy: layouts must match");
     TORCH_CHECK(srcs[t].scalar_type() == dsts[t].scalar_type());
     const int es = srcs[t].element_size();
     TORCH_CHECK(es == 2 || es == 4, "fused_copy: 2- or 4-byte elems");
-    long n = srcs[t].numel();
-    char* sp = (char*)srcs[t].data_ptr();
+    const char* sp = (const char*)srcs[t].data_ptr();
     char* dp = (char*)dsts[t].data_ptr();
-    for (long off = 0; off < n; off += CHUNK) {
-      Chunk c{};
-      c.p = sp + off * es;
-      c.g = dp + off * es;
-      c.n = (int)std::min<long>(CHUNK, n - off);
-      c.tensor_idx = es;  // element size flag
-      chunks.push_back(c);
-    }
+    for_each_chunk(srcs[t].numel(), [&](long off, int n) {
+      recs.push_back({sp + off * es, dp + off * es, n, es});
+    });
   }
-  auto host = at::from_blob(chunks.data(),
-                            {(long)(chunks.size() * sizeof(Chunk))},
-                            at::TensorOptions().dtype(at::kByte));
-  auto dev_chunks = host.to(srcs[0].device());
-  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  hipLaunchKernelGGL(copy_mt_kernel, dim3((int)chunks.size()), dim3(256), 0,
-                     stream,
-                     reinterpret_cast<const Chunk*>(dev_chunks.data_ptr()));
-  HIP_CHECK_LAST();
+  if (recs.empty()) return;
+  auto table = upload(recs, srcs[0].device());
+  launch_mt(copy_mt_kernel, (long)recs.size(),
+            reinterpret_cast<const CopyRec*>(table.data_ptr()));
 }

@@ -44,18 +44,45 @@ def _cpu_clip_stats(grads, max_norm, stats):
     return float(coef)
 
 
-class _GradClipMixin:
-    """``max_grad_norm`` support shared by the fused optimizers.
+def _norm_pass(ext, tables, partials, stats, max_norm, max_norm_buf=None):
+    """The GPU norm pass: per-chunk squared norms of every table into
+    ``partials`` at running offsets, then one finalize launch fills
+    stats = [norm, coefficient, non-finite count]. ``max_norm_buf`` (a
+    device scalar) overrides the host ``max_norm`` when given."""
+    off = 0
+    for table, nchunks, esize in tables:
+        ext.grad_sqnorm(table, nchunks, esize, partials, off)
+        off += nchunks
+    ext.grad_norm_finalize(partials, off, stats, max_norm, max_norm_buf)
 
-    The option is a plain attribute (NOT a param-group default): it stays
-    out of ``state_dict`` so old checkpoints load unchanged and the owner
-    (Node / ComputeEngine) re-supplies it on resume. The norm spans every
-    param group of the optimizer.
+
+class _FusedOptimizer(Optimizer):
+    """The step shared by the fused optimizers: collect every group's
+    lists, upload ONE chunk table per GPU group, then run the update
+    kernel(s) from it — with ``max_grad_norm`` set, after a norm pass over
+    all tables whose coefficient the update reads from ``stats``.
+
+    A subclass supplies
+      _collect(group) -> lists (params first, grads second) of the params
+                         that have a grad, creating their state,
+      _table_lists(lists) -> the five lists of ``mt_build_table``,
+      _table_fn, the name of its ``fused_*_table`` entry point,
+      _update_args(group, lists) -> that call's arguments between the
+                         table triple and ``stats``, and
+      _cpu_update(group, lists, coef).
+
+    ``max_grad_norm`` is a plain attribute (NOT a param-group default): it
+    stays out of ``state_dict`` so old checkpoints load unchanged and the
+    owner (Node / ComputeEngine) re-supplies it on resume. The norm spans
+    every param group of the optimizer.
     """
 
-    max_grad_norm: float | None = None
     _clip_stats = None      # [norm, coefficient, non-finite count] fp32
     _clip_partials = None   # per-chunk partial sums (GPU path)
+
+    def __init__(self, params, defaults, max_grad_norm=None):
+        super().__init__(params, defaults)
+        self.max_grad_norm = max_grad_norm
 
     def _stats_on(self, device):
         st = self._clip_stats
@@ -81,63 +108,101 @@ class _GradClipMixin:
         the first one). Returned without any synchronisation."""
         return self._clip_stats
 
-    def _clip_tables(self, ext, work):
-        """GPU clip prologue. ``work`` is one (ps, gs, ms, vs, masters)
-        tuple per param group with grads. Uploads ONE chunk table per
-        group (shared by the norm kernel and the update kernel), reduces
-        the squared norm of all groups into one partials buffer and
-        finalizes [norm, coefficient, count]. Returns (tables, stats)."""
-        tables = [ext.mt_build_table(*w) for w in work]
-        total = sum(t[1] for t in tables)
-        device = work[0][0][0].device
-        stats = self._stats_on(device)
-        partials = self._partials_on(device, total)
-        off = 0
-        for table, nchunks, esize in tables:
-            ext.grad_sqnorm(table, nchunks, esize, partials, off)
-            off += nchunks
-        ext.grad_norm_finalize(partials, total, stats,
-                               float(self.max_grad_norm))
-        return tables, stats
-
     def _masters(self, ps):
         return ([self.state[p]["master"] for p in ps]
-                if ps[0].dtype == torch.bfloat16 else [])
+                if ps and ps[0].dtype == torch.bfloat16 else [])
 
-    def _step_clipped(self):
-        """step() with max_grad_norm set: norm over ALL groups first, then
-        each group's update with the coefficient. The optimizer supplies
-        _collect(group) -> lists (params first, grads second),
-        _table_lists(lists) -> the five build-table lists,
-        _update_from_table(...) and _cpu_update(group, lists, coef)."""
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
         work = []
         for group in self.param_groups:
             lists = self._collect(group)
             if lists[0]:
                 work.append((group, lists))
         if not work:
-            return
-        grads = [g for _, lists in work for g in lists[1]]
-        if _on_gpu(grads):
-            ext = get_ext(required=True)
-            tables, stats = self._clip_tables(
-                ext, [self._table_lists(lists) for _, lists in work])
-            for (group, lists), table in zip(work, tables):
-                self._update_from_table(ext, group, lists, table, stats)
+            return loss
+        clip = self.max_grad_norm is not None
+        if clip:
+            # one norm over all groups: GPU or CPU is decided once
+            grads = [g for _, lists in work for g in lists[1]]
+            gpu_work, cpu_work = (work, []) if _on_gpu(grads) else ([], work)
         else:
-            stats = self._stats_on("cpu")
-            coef = _cpu_clip_stats(grads, float(self.max_grad_norm), stats)
-            for group, lists in work:
+            # independent groups, which may sit on different devices
+            gpu_work = [w for w in work if _on_gpu(w[1][0])]
+            cpu_work = [w for w in work if not _on_gpu(w[1][0])]
+        if gpu_work:
+            ext = get_ext(required=True)
+            update = getattr(ext, self._table_fn)
+            # arguments first: nothing but the launch then stands between
+            # a table's blocking upload and the kernel that reads it
+            args = [self._update_args(group, lists)
+                    for group, lists in gpu_work]
+            # one table per group, shared by the norm and update kernels
+            tables = [ext.mt_build_table(*self._table_lists(lists))
+                      for _, lists in gpu_work]
+            stats = None
+            if clip:
+                device = gpu_work[0][1][0][0].device
+                stats = self._stats_on(device)
+                partials = self._partials_on(device,
+                                             sum(t[1] for t in tables))
+                _norm_pass(ext, tables, partials, stats,
+                           float(self.max_grad_norm))
+            for table, a in zip(tables, args):
+                update(*table, *a, stats)
+        if cpu_work:
+            coef = None
+            if clip:
+                coef = _cpu_clip_stats(grads, float(self.max_grad_norm),
+                                       self._stats_on("cpu"))
+            for group, lists in cpu_work:
                 self._cpu_update(group, lists, coef)
+        return loss
 
 
-class FusedAdam(_GradClipMixin, Optimizer):
+class _MomentsOptimizer(_FusedOptimizer):
+    """State shared by Adam and LAMB: a step count, two fp32 moments and,
+    for bf16 params on the GPU, an fp32 master copy."""
+
+    def _init_state(self, p):
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = 0
+            st["m"] = torch.zeros_like(p, dtype=torch.float32)
+            st["v"] = torch.zeros_like(p, dtype=torch.float32)
+            if p.dtype == torch.bfloat16 and p.is_cuda:
+                st["master"] = p.detach().float().clone()
+        return st
+
+    def _collect(self, group):
+        ps, gs, ms, vs = [], [], [], []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            st = self._init_state(p)
+            st["step"] += 1
+            ps.append(p)
+            gs.append(p.grad)
+            ms.append(st["m"])
+            vs.append(st["v"])
+        return ps, gs, ms, vs
+
+    def _bias_corrections(self, group, ps):
+        b1, b2 = group["betas"]
+        step = self.state[ps[0]]["step"]
+        return 1 - b1 ** step, 1 - b2 ** step
+
+    def _table_lists(self, lists):
+        return (*lists, self._masters(lists[0]))
+
+
+class FusedAdam(_MomentsOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps,
                         weight_decay=weight_decay)
-        super().__init__(params, defaults)
-        self.max_grad_norm = max_grad_norm
+        super().__init__(params, defaults, max_grad_norm)
         self._graph = None  # hipGraph-capture buffers (see graph_step)
 
     # ---- hipGraph capture support (engine/graphstep.py) --------------
@@ -171,13 +236,7 @@ class FusedAdam(_GradClipMixin, Optimizer):
     def _ensure_state(self):
         for group in self.param_groups:
             for p in group["params"]:
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["m"] = torch.zeros_like(p, dtype=torch.float32)
-                    st["v"] = torch.zeros_like(p, dtype=torch.float32)
-                    if p.dtype == torch.bfloat16 and p.is_cuda:
-                        st["master"] = p.detach().float().clone()
+                self._init_state(p)
 
     def sync_lr(self):
         """Host -> device lr (and max_grad_norm) refresh; call OUTSIDE the
@@ -216,10 +275,8 @@ class FusedAdam(_GradClipMixin, Optimizer):
             grads.append(p.grad)
         ms = [self.state[p]["m"] for p in ps]
         vs = [self.state[p]["v"] for p in ps]
-        masters = ([self.state[p]["master"] for p in ps]
-                   if ps and ps[0].dtype == torch.bfloat16 else [])
-        self._graph["table"] = ext.adam_build_table(ps, grads, ms, vs,
-                                                    masters)
+        self._graph["table"] = ext.mt_build_table(ps, grads, ms, vs,
+                                                  self._masters(ps))
         self._graph["grads"] = grads
         if self._graph["clip"]:
             # preallocated outside the capture: replays reuse the buffer
@@ -238,74 +295,20 @@ class FusedAdam(_GradClipMixin, Optimizer):
         g["step"].add_(1)
         group = self.param_groups[0]
         b1, b2 = group["betas"]
-        table, nchunks, esize = g["table"]
+        stats = None
         if g["clip"]:
             stats = self._clip_stats
-            ext.grad_sqnorm(table, nchunks, esize, g["partials"], 0)
-            ext.grad_norm_finalize(g["partials"], nchunks, stats, 0.0,
-                                   g["max_norm"])
-            ext.fused_adam_graph(table, nchunks, esize, g["lr"], b1, b2,
-                                 group["eps"], group["weight_decay"],
-                                 g["step"], stats)
-            return
-        ext.fused_adam_graph(table, nchunks, esize, g["lr"], b1, b2,
-                             group["eps"], group["weight_decay"],
-                             g["step"])
+            _norm_pass(ext, [g["table"]], g["partials"], stats, 0.0,
+                       g["max_norm"])
+        ext.fused_adam_graph(*g["table"], g["lr"], b1, b2, group["eps"],
+                             group["weight_decay"], g["step"], stats)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        if self.max_grad_norm is not None:
-            self._step_clipped()
-            return loss
-        for group in self.param_groups:
-            ps, gs, ms, vs = lists = self._collect(group)
-            if not ps:
-                continue
-            b1, b2 = group["betas"]
-            bc1, bc2 = self._bias_corrections(group, ps)
-            if _on_gpu(ps):
-                ext = get_ext(required=True)
-                masters = ([self.state[p]["master"] for p in ps]
-                           if ps[0].dtype == torch.bfloat16 else [])
-                ext.fused_adam(ps, gs, ms, vs, masters, group["lr"], b1, b2,
-                               group["eps"], group["weight_decay"], bc1, bc2)
-            else:
-                self._cpu_update(group, lists, None)
-        return loss
+    _table_fn = "fused_adam_table"
 
-    def _collect(self, group):
-        ps, gs, ms, vs = [], [], [], []
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            st = self.state[p]
-            if len(st) == 0:
-                st["step"] = 0
-                st["m"] = torch.zeros_like(p, dtype=torch.float32)
-                st["v"] = torch.zeros_like(p, dtype=torch.float32)
-                if p.dtype == torch.bfloat16 and p.is_cuda:
-                    st["master"] = p.detach().float().clone()
-            st["step"] += 1
-            ps.append(p)
-            gs.append(p.grad)
-            ms.append(st["m"])
-            vs.append(st["v"])
-        return ps, gs, ms, vs
-
-    def _bias_corrections(self, group, ps):
+    def _update_args(self, group, lists):
         b1, b2 = group["betas"]
-        step = self.state[ps[0]]["step"]
-        return 1 - b1 ** step, 1 - b2 ** step
-
-    def _table_lists(self, lists):
-        return (*lists, self._masters(lists[0]))
-
-    def _update_from_table(self, ext, group, lists, table, stats):
-        b1, b2 = group["betas"]
-        bc1, bc2 = self._bias_corrections(group, lists[0])
-        ext.fused_adam_table(*table, group["lr"], b1, b2, group["eps"],
-                             group["weight_decay"], bc1, bc2, stats)
+        return (group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                *self._bias_corrections(group, lists[0]))
 
     def _cpu_update(self, group, lists, coef):
         b1, b2 = group["betas"]
@@ -323,13 +326,12 @@ class FusedAdam(_GradClipMixin, Optimizer):
                    alpha=-group["lr"])
 
 
-class FusedSGD(_GradClipMixin, Optimizer):
+class FusedSGD(_FusedOptimizer):
     def __init__(self, params, lr=1e-2, momentum=0.0, weight_decay=0.0,
                  nesterov=False, max_grad_norm=None):
         defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
                         nesterov=nesterov)
-        super().__init__(params, defaults)
-        self.max_grad_norm = max_grad_norm
+        super().__init__(params, defaults, max_grad_norm)
 
     def _collect(self, group):
         ps, gs, bufs = [], [], []
@@ -354,10 +356,11 @@ class FusedSGD(_GradClipMixin, Optimizer):
         ps, gs, bufs = lists
         return ps, gs, bufs, [], self._masters(ps)
 
-    def _update_from_table(self, ext, group, lists, table, stats):
-        ext.fused_sgd_table(*table, group["lr"], group["momentum"],
-                            group["weight_decay"], bool(group["nesterov"]),
-                            stats)
+    _table_fn = "fused_sgd_table"
+
+    def _update_args(self, group, lists):
+        return (group["lr"], group["momentum"], group["weight_decay"],
+                bool(group["nesterov"]))
 
     def _cpu_update(self, group, lists, coef):
         mom = group["momentum"]
@@ -372,29 +375,8 @@ class FusedSGD(_GradClipMixin, Optimizer):
                 gf = gf.add(b, alpha=mom) if group["nesterov"] else b
             p.add_(gf.to(p.dtype), alpha=-group["lr"])
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        if self.max_grad_norm is not None:
-            self._step_clipped()
-            return loss
-        for group in self.param_groups:
-            ps, gs, bufs = lists = self._collect(group)
-            if not ps:
-                continue
-            if _on_gpu(ps):
-                ext = get_ext(required=True)
-                masters = ([self.state[p]["master"] for p in ps]
-                           if ps[0].dtype == torch.bfloat16 else [])
-                ext.fused_sgd(ps, gs, bufs, masters, group["lr"],
-                              group["momentum"], group["weight_decay"],
-                              bool(group["nesterov"]))
-            else:
-                self._cpu_update(group, lists, None)
-        return loss
 
-
-class FusedLAMB(_GradClipMixin, Optimizer):
+class FusedLAMB(_MomentsOptimizer):
     """LAMB (You et al.) with the per-tensor trust ratio
     clamp(|w| / |update|). Parity: torch_optimizer.Lamb used by the BERT
     example (examples/bert/provider.py:49-50)."""
@@ -403,44 +385,16 @@ class FusedLAMB(_GradClipMixin, Optimizer):
                  weight_decay=0.0, clamp_trust=10.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps,
                         weight_decay=weight_decay, clamp_trust=clamp_trust)
-        super().__init__(params, defaults)
-        self.max_grad_norm = max_grad_norm
+        super().__init__(params, defaults, max_grad_norm)
 
-    def _collect(self, group):
-        ps, gs, ms, vs = [], [], [], []
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            st = self.state[p]
-            if len(st) == 0:
-                st["step"] = 0
-                st["m"] = torch.zeros_like(p, dtype=torch.float32)
-                st["v"] = torch.zeros_like(p, dtype=torch.float32)
-                if p.dtype == torch.bfloat16 and p.is_cuda:
-                    st["master"] = p.detach().float().clone()
-            st["step"] += 1
-            ps.append(p)
-            gs.append(p.grad)
-            ms.append(st["m"])
-            vs.append(st["v"])
-        return ps, gs, ms, vs
+    _table_fn = "fused_lamb_table"
 
-    def _bias_corrections(self, group, ps):
+    def _update_args(self, group, lists):
         b1, b2 = group["betas"]
-        step = self.state[ps[0]]["step"]
-        return 1 - b1 ** step, 1 - b2 ** step
-
-    def _table_lists(self, lists):
-        return (*lists, self._masters(lists[0]))
-
-    def _update_from_table(self, ext, group, lists, table, stats):
-        b1, b2 = group["betas"]
-        bc1, bc2 = self._bias_corrections(group, lists[0])
-        table, nchunks, esize = table
-        ext.fused_lamb_table(table, nchunks, esize, len(lists[0]),
-                             group["lr"], b1, b2, group["eps"],
-                             group["weight_decay"], bc1, bc2,
-                             group["clamp_trust"], stats)
+        return (len(lists[0]), group["lr"], b1, b2, group["eps"],
+                group["weight_decay"],
+                *self._bias_corrections(group, lists[0]),
+                group["clamp_trust"])
 
     def _cpu_update(self, group, lists, coef):
         b1, b2 = group["betas"]
@@ -461,29 +415,6 @@ class FusedLAMB(_GradClipMixin, Optimizer):
                 (wn / un).clamp(max=group["clamp_trust"]),
                 torch.ones_like(wn))
             p.add_((trust * upd).to(p.dtype), alpha=-group["lr"])
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        if self.max_grad_norm is not None:
-            self._step_clipped()
-            return loss
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            ps, gs, ms, vs = lists = self._collect(group)
-            if not ps:
-                continue
-            bc1, bc2 = self._bias_corrections(group, ps)
-            if _on_gpu(ps):
-                ext = get_ext(required=True)
-                masters = ([self.state[p]["master"] for p in ps]
-                           if ps[0].dtype == torch.bfloat16 else [])
-                ext.fused_lamb(ps, gs, ms, vs, masters, group["lr"], b1, b2,
-                               group["eps"], group["weight_decay"], bc1, bc2,
-                               group["clamp_trust"])
-            else:
-                self._cpu_update(group, lists, None)
-        return loss
 
 
 @torch.no_grad()
@@ -521,11 +452,7 @@ def clip_grad_norm_(parameters, max_norm) -> torch.Tensor:
     total = sum(t[1] for t in tables)
     stats = torch.zeros(3, dtype=torch.float32, device=device)
     partials = torch.empty(max(total, 1), dtype=torch.float32, device=device)
-    off = 0
-    for table, nchunks, esize in tables:
-        ext.grad_sqnorm(table, nchunks, esize, partials, off)
-        off += nchunks
-    ext.grad_norm_finalize(partials, total, stats, float(max_norm))
+    _norm_pass(ext, tables, partials, stats, float(max_norm))
     for table, nchunks, esize in tables:
         ext.scale_mt(table, nchunks, esize, stats)
     return stats[0]

@@ -176,6 +176,58 @@ def test_fused_lamb_sane(dev):
             f"max err {(a.cpu()-b).abs().max()}"
 
 
+def test_fused_copy_mixed_dtypes_and_tails(dev):
+    """One fused_copy call over fp32 and bf16 tensors: a tail shorter than
+    one 16-byte vector (7), exactly one bf16 vector (8), body + tail
+    (4099), two chunks with a tail-only second one (65536 + 5) and a
+    channels_last tensor. Every destination sits 32 elements inside a
+    sentinel-filled buffer (16-byte aligned, as the vector body assumes)
+    with 32 sentinels after it."""
+    from ravnest_amd.ops import get_ext
+    ext = get_ext(True)
+    torch.manual_seed(0)
+    PAD, SENTINEL = 32, -7.0
+    srcs, dsts, bufs = [], [], []
+
+    def add(src, strides=None):
+        n = src.numel()
+        buf = torch.full((PAD + n + PAD,), SENTINEL, device=dev,
+                         dtype=src.dtype)
+        strides = src.stride() if strides is None else strides
+        dst = torch.as_strided(buf, src.shape, strides, storage_offset=PAD)
+        assert dst.data_ptr() % 16 == 0
+        srcs.append(src)
+        dsts.append(dst)
+        bufs.append(buf)
+
+    for dtype in (torch.float32, torch.bfloat16):
+        for n in (1, 7, 8, 4099, 65536 + 5):
+            add(torch.randn(n, device=dev).to(dtype))
+    cl = torch.randn(2, 3, 4, 5, device=dev).contiguous(
+        memory_format=torch.channels_last)
+    assert cl.stride() == (60, 1, 15, 3)
+    add(cl)
+
+    ext.fused_copy(srcs, dsts)
+    for src, dst, buf in zip(srcs, dsts, bufs):
+        assert dst.stride() == src.stride()
+        assert torch.equal(dst, src), (src.dtype, tuple(src.shape))
+        n = src.numel()
+        assert bool((buf[:PAD] == SENTINEL).all()), (src.dtype, n)
+        assert bool((buf[PAD + n:] == SENTINEL).all()), (src.dtype, n)
+
+    a = torch.randn(4, 6, device=dev)
+    with pytest.raises(RuntimeError):  # strides (6, 1) vs (1, 4)
+        ext.fused_copy([a], [torch.empty(6, 4, device=dev).t()])
+    with pytest.raises(RuntimeError):
+        ext.fused_copy([a], [torch.empty(4, 6, device=dev,
+                                         dtype=torch.bfloat16)])
+    # nothing to copy: returns before any launch (a zero-block launch
+    # would raise)
+    assert ext.fused_copy([], []) is None
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("causal,masked,S,D", [
     (False, False, 512, 64),
     (False, True, 512, 64),
