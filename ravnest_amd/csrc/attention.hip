@@ -21,6 +21,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "attention_kv_len.h"
 #include "common.h"
 
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
@@ -57,7 +58,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const bf16_t* __restrict__ v, const float* __restrict__ mask,
     bf16_t* __restrict__ o, float* __restrict__ lse, int S, int causal,
     float scale, int has_mask, long H,
-    Strides sq, Strides sk, Strides sv, Strides so) {
+    Strides sq, Strides sk, Strides sv, Strides so,
+    const int* __restrict__ kv_len) {
   constexpr int DSTEPS = D / 16;   // QK^T k-steps
   constexpr int DHALF = D / 32;    // PV column halves
   const int lane = threadIdx.x & (WAVE - 1);
@@ -94,7 +96,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   float m_run = -INFINITY;  // running max for qrow j32
   float l_run = 0.f;        // running sum for qrow j32
 
-  const int kv_end = causal ? min(S, q0 + 32) : S;
+  // keys >= L are never visited (whole tiles) or scored -inf (ragged)
+  const int L = kv_horizon(kv_len, b, S);
+  const int kv_end = min(causal ? min(S, q0 + 32) : S, L);
 
   for (int k0 = 0; k0 < kv_end; k0 += 32) {
     // ---- QK^T: A = K tile (i = key = j32 local), k = d ----
@@ -118,9 +122,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     for (int r = 0; r < 16; ++r) {
       const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
       float sv = s_acc[r] * scale;
-      if (key >= S) sv = -INFINITY;
+      if (key >= L) sv = -INFINITY;
       if (causal && key > qrow) sv = -INFINITY;
-      if (has_mask) sv += mp[key];  // additive (B,1,1,S) mask, see host
+      // additive (B,1,1,S) mask, see host; keys >= S are -inf already
+      if (has_mask) sv += mp[min(key, S - 1)];
       s_acc[r] = sv;
       tile_max = fmaxf(tile_max, sv);
     }
@@ -256,6 +261,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_lds_kernel(
     bf16_t* __restrict__ o, float* __restrict__ lse, int S, int causal,
     float scale, int has_mask, long H,
     Strides sq, Strides sk, Strides sv, Strides so,
+    const int* __restrict__ kv_len,
     float pdrop = 0.f, float inv_keep = 1.f,
     unsigned long long dseed = 0,
     const long long* __restrict__ seed_buf = nullptr,
@@ -319,7 +325,10 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_lds_kernel(
   // MFMA/softmax phase; double-buffered slots make the LDS write safe
   // after compute (the slot's last readers passed the barrier at the top
   // of THIS iteration).
-  const int kv_all = causal ? min(S, blockIdx.x * 128 + 128) : S;
+  // A per-sequence key horizon L (kv_len) only lowers that bound: it is
+  // uniform per block, so barriers and have_next stay consistent.
+  const int L = kv_horizon(kv_len, b, S);
+  const int kv_all = min(causal ? min(S, blockIdx.x * 128 + 128) : S, L);
   // K tile rides global_load_lds (lane-linear dest; the XOR swizzle
   // becomes the closed-form source inverse — see attention_bwd.hip).
   // V cannot: its TR16 image uses 144-byte padded rows, which a
@@ -377,7 +386,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_lds_kernel(
       for (int r = 0; r < 16; ++r) {
         const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float sv2 = s_acc[r] * scale;
-        if (key >= S) sv2 = -INFINITY;
+        if (key >= L) sv2 = -INFINITY;
         if (causal && key > qrow) sv2 = -INFINITY;
         if (has_mask) sv2 += __shfl(mload, key - k0, WAVE);
         s_acc[r] = sv2;
@@ -534,6 +543,25 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_lds_kernel(
         (l_run > 0.f) ? m_run + __logf(l_run) : -INFINITY;
 }
 
+// ---- per-sequence key horizon from the additive padding mask --------
+// kv_len[b] = 1 + (last j with mask[b,j] > -10000), or S when the row has
+// no live key (such a row then runs exactly as without a horizon). A key
+// at <= -10000 contributes exp(-10000 + s - m) == 0 once any live key set
+// the running max, so dropping the dead TAIL changes no output bit. One
+// block per row; runs on the stream, so the bound follows the mask's
+// contents at every graph replay.
+__global__ __launch_bounds__(256) void attn_mask_kv_len_kernel(
+    const float* __restrict__ mask, int* __restrict__ kv_len, int S) {
+  __shared__ float red[4];
+  const float* mp = mask + blockIdx.x * (long)S;
+  int last = -1;
+  for (int j = threadIdx.x; j < S; j += blockDim.x)
+    if (mp[j] > -10000.f) last = j;  // j ascends per thread
+  // indices < 2^24 are exact in fp32 (S is checked on the host)
+  const float m = block_max((float)last, red);
+  if (threadIdx.x == 0) kv_len[blockIdx.x] = (m < 0.f) ? S : (int)m + 1;
+}
+
 // ---- layout probe: one wave computes one 32x32x16 tile --------------
 __global__ void mfma_probe_kernel(const bf16_t* __restrict__ a,
                                   const bf16_t* __restrict__ b,
@@ -572,8 +600,35 @@ static const bool use_tr16 = [] {
   return !(e && e[0] == '0');  // default: hardware-transpose V reads
 }();
 
+// optional per-sequence key counts -> device pointer (nullptr = none)
+const int* attn_kv_len_ptr(const c10::optional<at::Tensor>& kv_len, long B) {
+  if (!kv_len.has_value()) return nullptr;
+  TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt &&
+                  kv_len->is_contiguous() && kv_len->numel() == B,
+              "kv_len must be a contiguous int32 CUDA tensor with one entry "
+              "per batch row");
+  return kv_len->data_ptr<int>();
+}
+
+at::Tensor attn_mask_kv_len(at::Tensor mask) {
+  TORCH_CHECK(mask.is_cuda() && mask.dim() >= 2,
+              "attn_mask_kv_len: (B,S) or (B,1,1,S) CUDA mask");
+  const long B = mask.size(0), S = mask.size(-1);
+  TORCH_CHECK(mask.numel() == B * S && S > 0 && S < (1 << 24),
+              "attn_mask_kv_len: mask must hold one value per (batch, key)");
+  auto mask_f = mask.to(at::kFloat).reshape({B, S}).contiguous();
+  auto out = at::empty({B}, mask.options().dtype(at::kInt));
+  if (B == 0) return out;
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  hipLaunchKernelGGL(attn_mask_kv_len_kernel, dim3(B), dim3(256), 0, stream,
+                     mask_f.data_ptr<float>(), out.data_ptr<int>(), (int)S);
+  HIP_CHECK_LAST();
+  return out;
+}
+
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 at::Tensor mask, bool causal, double scale) {
+                                 at::Tensor mask, bool causal, double scale,
+                                 c10::optional<at::Tensor> kv_len) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
               v.is_contiguous());
   TORCH_CHECK(q.dim() == 4, "q must be (B,H,S,D)");
@@ -582,6 +637,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   const long B = q.size(0), H = q.size(1);
   const int S = q.size(2), D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "attn_fwd: head_dim 64 or 128");
+  const int* kvl = attn_kv_len_ptr(kv_len, B);
 
   auto o = at::empty_like(q);
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
@@ -607,18 +663,18 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                          stream, QP, KP, VP, mask_ptr,                      \
                          OP, lse.data_ptr<float>(), S,                      \
                          causal ? 1 : 0, (float)scale, has_mask ? 1 : 0,    \
-                         (long)H, SQ, SK, SV, SO);                          \
+                         (long)H, SQ, SK, SV, SO, kvl);                          \
     else if (DD == 64 && use_lds_fwd)                                       \
       hipLaunchKernelGGL((attn_fwd_lds_kernel<false>), grid, block, 0,      \
                          stream, QP,                                        \
                          KP, VP, mask_ptr, OP, lse.data_ptr<float>(), S,    \
                          causal ? 1 : 0, (float)scale, has_mask ? 1 : 0,    \
-                         (long)H, SQ, SK, SV, SO);                          \
+                         (long)H, SQ, SK, SV, SO, kvl);                          \
     else                                                                    \
       hipLaunchKernelGGL((attn_fwd_kernel<DD>), grid, block, 0, stream, QP, \
                          KP, VP, mask_ptr, OP, lse.data_ptr<float>(), S,    \
                          causal ? 1 : 0, (float)scale, has_mask ? 1 : 0,    \
-                         (long)H, SQ, SK, SV, SO);                          \
+                         (long)H, SQ, SK, SV, SO, kvl);                          \
   } while (0)
 
   if (D == 64) {
@@ -643,7 +699,8 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
 std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                                      bool causal, double scale,
                                      double pdrop, int64_t dseed,
-                                     c10::optional<at::Tensor> seed_buf) {
+                                     c10::optional<at::Tensor> seed_buf,
+                                     c10::optional<at::Tensor> kv_len) {
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous());
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3,
               "qkv must be (B,S,3,H,D)");
@@ -651,6 +708,7 @@ std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
   const long B = qkv.size(0), H = qkv.size(3);
   const int S = qkv.size(1), D = qkv.size(4);
   TORCH_CHECK(D == 64 || D == 128, "attn_fwd_qkv: head_dim 64 or 128");
+  const int* kvl = attn_kv_len_ptr(kv_len, B);
 
   auto o = at::empty({B, (long)S, H, (long)D}, qkv.options());
   auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
@@ -685,7 +743,7 @@ std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                        reinterpret_cast<bf16_t*>(o.data_ptr()),
                        lse.data_ptr<float>(), S, causal ? 1 : 0,
                        (float)scale, has_mask ? 1 : 0, (long)H, sp, sp, sp,
-                       so, (float)pdrop, 1.f / (1.f - (float)pdrop),
+                       so, kvl, (float)pdrop, 1.f / (1.f - (float)pdrop),
                        (unsigned long long)dseed, sb,
                        reinterpret_cast<unsigned*>(mbits.data_ptr<int>()));
     HIP_CHECK_LAST();

@@ -17,6 +17,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "attention_kv_len.h"
 #include "common.h"
 
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
@@ -120,6 +121,20 @@ DEVINL void acc_to_afrag(const f32x16& acc, unsigned int pa[2][4]) {
   }
 }
 
+// A key block wholly past the sequence's key horizon has P == 0 for every
+// query: its gradient rows are exact zeros. Each wave stores its 32 rows.
+DEVINL void store_zero_rows(bf16_t* __restrict__ gp, int k0, int S,
+                            long rs, int hi, int j32) {
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int krow = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      if (krow < S) gp[(long)krow * rs + hh * 32 + j32] = f2bf(0.f);
+    }
+  }
+}
+
 // Delta[row] = sum_d dO[row][d] * O[row][d]. D/8 lanes per row, bf16x8
 // loads (the one-wave-per-row 2-B-scalar version measured 7x off the
 // bandwidth bound at 2.5% of the BERT step — rocprofv3 r01 final).
@@ -158,8 +173,8 @@ __global__ __launch_bounds__(256, DROP ? 4 : 5) void attn_bwd_dv_kernel(
     const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ mask, bf16_t* __restrict__ dv, int S,
     int causal, float scale, int has_mask, long H, StridesB sio,
-    StridesB sdo, StridesB sg, float inv_keep = 1.f,
-    const unsigned* __restrict__ mbits = nullptr) {
+    StridesB sdo, StridesB sg, const int* __restrict__ kv_len,
+    float inv_keep = 1.f, const unsigned* __restrict__ mbits = nullptr) {
   constexpr int D = 64;
   // block-shared tiles: dO (linear: 2B B-operand reads) and Q
   // (((row&15)<<4)-swizzled: conflict-free b128 A-fragment reads).
@@ -183,6 +198,15 @@ __global__ __launch_bounds__(256, DROP ? 4 : 5) void attn_bwd_dv_kernel(
   bf16_t* dvp = dv + b * sg.bs + h * sg.hs;
   const float* lsep = lse + bh * (long)S;
   const float* mp = has_mask ? (mask + b * (long)S) : nullptr;
+  // key horizon: block-uniform exit before the first barrier. In the
+  // block that straddles L, a wave whose 32 keys all lie past it skips
+  // its compute (k0 < L below) and stores its zero accumulators; it also
+  // never reads the fwd's mask words for tiles the fwd did not visit.
+  const int L = kv_horizon(kv_len, b, S);
+  if ((int)blockIdx.x * 128 >= L) {
+    if (live_wave) store_zero_rows(dvp, k0, S, sg.rs, hi, j32);
+    return;
+  }
   const bool lse_in_lds = S <= 2048;
   if (lse_in_lds) {
     for (int i = threadIdx.x; i < S; i += blockDim.x) lse_lds[i] = lsep[i];
@@ -242,7 +266,7 @@ __global__ __launch_bounds__(256, DROP ? 4 : 5) void attn_bwd_dv_kernel(
     const bool have_next = q0 + 32 < S;
     if (have_next)  // T14: next tile's LDS-DMA under this compute
       stage2(q0 + 32, smem + (slot ^ 1) * 8192);
-    const bool compute = live_wave && (!causal || q0 + 31 >= k0);
+    const bool compute = live_wave && k0 < L && (!causal || q0 + 31 >= k0);
     if (compute) {
     f32x16 s_acc;
 #pragma unroll
@@ -264,7 +288,7 @@ __global__ __launch_bounds__(256, DROP ? 4 : 5) void attn_bwd_dv_kernel(
       const int qclmp = min(qrow, S - 1);
       const float l = lse_in_lds ? lse_lds[qclmp] : lsep[qclmp];
       float sv = s_acc[r] * scale + mask_val;
-      bool dead = (qrow >= S) || (key >= S) || (causal && key > qrow) ||
+      bool dead = (qrow >= S) || (key >= L) || (causal && key > qrow) ||
                   !isfinite(l);
       s_acc[r] = dead ? 0.f : __expf(sv - l);  // P
       if constexpr (DROP)  // dV uses the DROPPED probabilities
@@ -313,8 +337,8 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dk_kernel(
     const float* __restrict__ lse, const float* __restrict__ delta,
     const float* __restrict__ mask, bf16_t* __restrict__ dk, int S,
     int causal, float scale, int has_mask, long H, StridesB sio,
-    StridesB sdo, StridesB sg, float inv_keep = 1.f,
-    const unsigned* __restrict__ mbits = nullptr) {
+    StridesB sdo, StridesB sg, const int* __restrict__ kv_len,
+    float inv_keep = 1.f, const unsigned* __restrict__ mbits = nullptr) {
   constexpr int D = 64;
   // Q tile swizzled (b128 A-frags for S, XOR-adjusted u16 B-reads for
   // dK) + dO tile swizzled (b128 A-frags for dP); double-buffered.
@@ -340,6 +364,14 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dk_kernel(
   const float* lsep = lse + bh * (long)S;
   const float* dltp = delta + bh * (long)S;
   const float* mp = has_mask ? (mask + b * (long)S) : nullptr;
+  // key horizon: block-uniform exit before the first barrier
+  const int L = kv_horizon(kv_len, b, S);
+  if ((int)blockIdx.x * 128 >= L) {
+    if (live_wave) {
+      store_zero_rows(dkp, k0, S, sg.rs, hi, j32);
+    }
+    return;
+  }
   const bool lse_in_lds = S <= 2048;
   if (lse_in_lds) {
     for (int i = threadIdx.x; i < S; i += blockDim.x) {
@@ -400,7 +432,7 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dk_kernel(
     const bool have_next = q0 + 32 < S;
     if (have_next)  // T14: next tile's LDS-DMA under this compute
       stage2(q0 + 32, smem + (slot ^ 1) * 8192);
-    const bool compute = live_wave && (!causal || q0 + 31 >= k0);
+    const bool compute = live_wave && k0 < L && (!causal || q0 + 31 >= k0);
     if (compute) {
     f32x16 s_acc, dp_acc;
 #pragma unroll
@@ -429,7 +461,7 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dk_kernel(
       const float l = lse_in_lds ? lse_lds[qclmp] : lsep[qclmp];
       const float dlt = lse_in_lds ? dlt_lds[qclmp] : dltp[qclmp];
       float sv = s_acc[r] * scale + mask_val;
-      bool dead = (qrow >= S) || (key >= S) || (causal && key > qrow) ||
+      bool dead = (qrow >= S) || (key >= L) || (causal && key > qrow) ||
                   !isfinite(l);
       const float p = dead ? 0.f : __expf(sv - l);
       float dpr = dp_acc[r];
@@ -483,7 +515,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dvdk_kernel(
     const float* __restrict__ lse, const float* __restrict__ delta,
     const float* __restrict__ mask, bf16_t* __restrict__ dk,
     bf16_t* __restrict__ dv, int S, int causal, float scale, int has_mask,
-    long H, StridesB sio, StridesB sdo, StridesB sg) {
+    long H, StridesB sio, StridesB sdo, StridesB sg,
+    const int* __restrict__ kv_len) {
   constexpr int D = 64;
   __shared__ __attribute__((aligned(16))) char smem[16384 + 16384];
   float* lse_lds = reinterpret_cast<float*>(smem + 16384);
@@ -506,6 +539,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dvdk_kernel(
   const float* lsep = lse + bh * (long)S;
   const float* dltp = delta + bh * (long)S;
   const float* mp = has_mask ? (mask + b * (long)S) : nullptr;
+  // key horizon: block-uniform exit before the first barrier
+  const int L = kv_horizon(kv_len, b, S);
+  if ((int)blockIdx.x * 128 >= L) {
+    if (live_wave) {
+      store_zero_rows(dkp, k0, S, sg.rs, hi, j32);
+      store_zero_rows(dvp, k0, S, sg.rs, hi, j32);
+    }
+    return;
+  }
   const bool lse_in_lds = S <= 2048;
   if (lse_in_lds) {
     for (int i = threadIdx.x; i < S; i += blockDim.x) {
@@ -569,7 +611,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dvdk_kernel(
     const bool have_next = q0 + 32 < S;
     if (have_next)  // T14: next tile's LDS-DMA under this compute
       stage2(q0 + 32, smem + (slot ^ 1) * 8192);
-    const bool compute = live_wave && (!causal || q0 + 31 >= k0);
+    const bool compute = live_wave && k0 < L && (!causal || q0 + 31 >= k0);
     if (compute) {
       f32x16 s_acc, dp_acc;
 #pragma unroll
@@ -595,7 +637,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dvdk_kernel(
         const float l = lse_in_lds ? lse_lds[qclmp] : lsep[qclmp];
         const float dlt = lse_in_lds ? dlt_lds[qclmp] : dltp[qclmp];
         float sv = s_acc[r] * scale + mask_val;
-        bool dead = (qrow >= S) || (key >= S) || (causal && key > qrow) ||
+        bool dead = (qrow >= S) || (key >= L) || (causal && key > qrow) ||
                     !isfinite(l);
         const float p = dead ? 0.f : __expf(sv - l);
         s_acc[r] = p;                                          // P
@@ -657,8 +699,8 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dq_kernel(
     const float* __restrict__ lse, const float* __restrict__ delta,
     const float* __restrict__ mask, bf16_t* __restrict__ dq, int S,
     int causal, float scale, int has_mask, long H, StridesB sio,
-    StridesB sdo, StridesB sg, float inv_keep = 1.f,
-    const unsigned* __restrict__ mbits = nullptr) {
+    StridesB sdo, StridesB sg, const int* __restrict__ kv_len,
+    float inv_keep = 1.f, const unsigned* __restrict__ mbits = nullptr) {
   constexpr int D = 64;
   // K tile swizzled (b128 A-frags for S^T, XOR-adjusted u16 B-reads for
   // dQ) + V tile swizzled (b128 A-frags for dP^T); double-buffered
@@ -701,7 +743,9 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dq_kernel(
     for (int r = 0; r < 16; ++r) dq_acc[h][r] = 0.f;
 
   // block-wide kv range (barriers are block-wide); waves guard compute
-  const int kv_end = causal ? min(S, blockIdx.x * 128 + 128) : S;
+  // (lowered to the sequence's key horizon L; uniform per block)
+  const int L = kv_horizon(kv_len, b, S);
+  const int kv_end = min(causal ? min(S, blockIdx.x * 128 + 128) : S, L);
   // glds staging: K and V tiles, source-side inverse of the XOR
   // swizzle (see the dv kernel's comment)
   const int wdst = ((int)threadIdx.x >> 6) * 1024;
@@ -764,7 +808,7 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dq_kernel(
       const int kk = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
       float sv = s_acc[r] * scale;
       if (has_mask && kk < S) sv += __shfl(mload, kk - k0, WAVE);
-      bool dead = (qrow >= S) || (kk >= S) || (causal && kk > qrow) ||
+      bool dead = (qrow >= S) || (kk >= L) || (causal && kk > qrow) ||
                   !isfinite(l_row);
       const float p = dead ? 0.f : __expf(sv - l_row);
       float dpr = dp_acc[r];
@@ -807,16 +851,12 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dq_kernel(
   }
 }
 
-}  // namespace
-
-namespace {
-
 std::vector<at::Tensor> attn_bwd_impl(
     const bf16_t* qb, const bf16_t* kb, const bf16_t* vb, const bf16_t* ob,
     const bf16_t* dob, at::Tensor lse, const float* mask_ptr, bool has_mask,
     bool causal, double scale, long B, long H, int S, StridesB sio,
     StridesB sdo, StridesB sg, bf16_t* dqb, bf16_t* dkb, bf16_t* dvb,
-    const at::TensorOptions& fopt, float pdrop = 0.f,
+    const at::TensorOptions& fopt, const int* kvl, float pdrop = 0.f,
     const unsigned* mbits = nullptr) {
   const float inv_keep = 1.f / (1.f - pdrop);
   auto delta = at::empty({B * H * (long)S}, fopt);
@@ -840,17 +880,17 @@ std::vector<at::Tensor> attn_bwd_impl(
     hipLaunchKernelGGL((attn_bwd_dv_kernel<true>), gridk, block, 0, stream,
                        qb, kb, dob, lse.data_ptr<float>(), mask_ptr, dvb, S,
                        causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg, inv_keep, mbits);
+                       sio, sdo, sg, kvl, inv_keep, mbits);
     hipLaunchKernelGGL((attn_bwd_dk_kernel<true>), gridk, block, 0, stream,
                        qb, kb, vb, dob, lse.data_ptr<float>(),
                        delta.data_ptr<float>(), mask_ptr, dkb, S,
                        causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg, inv_keep, mbits);
+                       sio, sdo, sg, kvl, inv_keep, mbits);
     hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), gridk, block, 0, stream,
                        qb, kb, vb, dob, lse.data_ptr<float>(),
                        delta.data_ptr<float>(), mask_ptr, dqb, S,
                        causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg, inv_keep, mbits);
+                       sio, sdo, sg, kvl, inv_keep, mbits);
     HIP_CHECK_LAST();
     return {};
   }
@@ -859,25 +899,25 @@ std::vector<at::Tensor> attn_bwd_impl(
                        qb, kb,
                        dob, lse.data_ptr<float>(), mask_ptr, dvb, S,
                        causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg);
+                       sio, sdo, sg, kvl);
     hipLaunchKernelGGL((attn_bwd_dk_kernel<false>), gridk, block, 0, stream,
                        qb, kb,
                        vb, dob, lse.data_ptr<float>(),
                        delta.data_ptr<float>(), mask_ptr, dkb, S,
                        causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg);
+                       sio, sdo, sg, kvl);
   } else {
     hipLaunchKernelGGL(attn_bwd_dvdk_kernel, gridk, block, 0, stream, qb,
                        kb, vb, dob, lse.data_ptr<float>(),
                        delta.data_ptr<float>(), mask_ptr, dkb, dvb, S,
                        causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg);
+                       sio, sdo, sg, kvl);
   }
   hipLaunchKernelGGL((attn_bwd_dq_kernel<false>), gridk, block, 0, stream,
                      qb, kb,
                      vb, dob, lse.data_ptr<float>(), delta.data_ptr<float>(),
                      mask_ptr, dqb, S, causal ? 1 : 0, (float)scale,
-                     has_mask ? 1 : 0, H, sio, sdo, sg);
+                     has_mask ? 1 : 0, H, sio, sdo, sg, kvl);
   HIP_CHECK_LAST();
   return {};
 }
@@ -887,7 +927,8 @@ std::vector<at::Tensor> attn_bwd_impl(
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor dout,
                                  at::Tensor lse, at::Tensor mask, bool causal,
-                                 double scale) {
+                                 double scale,
+                                 c10::optional<at::Tensor> kv_len) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
               v.is_contiguous() && o.is_contiguous());
   TORCH_CHECK(q.scalar_type() == at::kBFloat16);
@@ -916,7 +957,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                 reinterpret_cast<bf16_t*>(dq.data_ptr()),
                 reinterpret_cast<bf16_t*>(dk.data_ptr()),
                 reinterpret_cast<bf16_t*>(dv.data_ptr()),
-                q.options().dtype(at::kFloat));
+                q.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B));
   return {dq, dk, dv};
 }
 
@@ -924,7 +965,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         at::Tensor lse, at::Tensor mask, bool causal,
                         double scale, double pdrop,
-                        c10::optional<at::Tensor> mbits) {
+                        c10::optional<at::Tensor> mbits,
+                        c10::optional<at::Tensor> kv_len) {
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && o.is_contiguous());
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3);
   const long B = qkv.size(0), H = qkv.size(3);
@@ -953,6 +995,7 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                 reinterpret_cast<const bf16_t*>(dc.data_ptr()), lse,
                 mask_ptr, has_mask, causal, scale, B, H, S, sp, sod, sp,
                 dbase, dbase + HD, dbase + 2 * HD,
-                qkv.options().dtype(at::kFloat), (float)pdrop, mb);
+                qkv.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B),
+                (float)pdrop, mb);
   return dqkv;
 }

@@ -108,19 +108,24 @@ void fused_lamb_table(at::Tensor table, long nchunks, long esize,
                       double clamp_trust, c10::optional<at::Tensor> gstats);
 void fused_copy(std::vector<at::Tensor> srcs, std::vector<at::Tensor> dsts);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 at::Tensor mask, bool causal, double scale);
+                                 at::Tensor mask, bool causal, double scale,
+                                 c10::optional<at::Tensor> kv_len);
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor dout,
                                  at::Tensor lse, at::Tensor mask, bool causal,
-                                 double scale);
+                                 double scale,
+                                 c10::optional<at::Tensor> kv_len);
 std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                                      bool causal, double scale,
                                      double pdrop, int64_t dseed,
-                                     c10::optional<at::Tensor> seed_buf);
+                                     c10::optional<at::Tensor> seed_buf,
+                                     c10::optional<at::Tensor> kv_len);
 at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         at::Tensor lse, at::Tensor mask, bool causal,
                         double scale, double pdrop,
-                        c10::optional<at::Tensor> mbits);
+                        c10::optional<at::Tensor> mbits,
+                        c10::optional<at::Tensor> kv_len);
+at::Tensor attn_mask_kv_len(at::Tensor mask);
 at::Tensor mfma_probe(at::Tensor a, at::Tensor b);
 at::Tensor tr16_probe();
 at::Tensor mfma_mx_probe(at::Tensor a, at::Tensor b, int64_t sa, int64_t sb);
@@ -222,18 +227,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2"),
         py::arg("clamp_trust"), py::arg("gstats") = py::none());
   m.def("fused_copy", &fused_copy, "multi-tensor device copy");
-  m.def("attn_fwd", &attn_fwd, "flash attention fwd (bf16, MFMA)");
-  m.def("attn_bwd", &attn_bwd, "flash attention bwd (bf16, MFMA, D=64)");
+  // kv_len: optional int32[B] per-sequence key counts; keys past it are
+  // skipped (whole tiles) or scored -inf (ragged tile)
+  m.def("attn_fwd", &attn_fwd,
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("mask"),
+        py::arg("causal"), py::arg("scale"), py::arg("kv_len") = py::none(),
+        "flash attention fwd (bf16, MFMA)");
+  m.def("attn_bwd", &attn_bwd,
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("dout"), py::arg("lse"), py::arg("mask"), py::arg("causal"),
+        py::arg("scale"), py::arg("kv_len") = py::none(),
+        "flash attention bwd (bf16, MFMA, D=64)");
   m.def("attn_fwd_qkv", &attn_fwd_qkv,
         py::arg("qkv"), py::arg("mask"), py::arg("causal"),
         py::arg("scale"), py::arg("pdrop") = 0.0, py::arg("dseed") = 0,
-        py::arg("seed_buf") = py::none(),
+        py::arg("seed_buf") = py::none(), py::arg("kv_len") = py::none(),
         "flash attention fwd, packed (B,S,3,H,D) qkv -> (B,S,H,D)");
   m.def("attn_bwd_qkv", &attn_bwd_qkv,
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("lse"),
         py::arg("mask"), py::arg("causal"), py::arg("scale"),
         py::arg("pdrop") = 0.0, py::arg("mbits") = py::none(),
+        py::arg("kv_len") = py::none(),
         "flash attention bwd, packed qkv -> dqkv");
+  m.def("attn_mask_kv_len", &attn_mask_kv_len, py::arg("mask"),
+        "additive (B,S) padding mask -> int32[B] key horizon");
   m.def("mfma_probe", &mfma_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 mapping probe");
   m.def("mfma_mx_probe", &mfma_mx_probe,

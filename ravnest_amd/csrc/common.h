@@ -30,6 +30,14 @@ DEVINL unsigned short f2us(float f) {
   return (unsigned short)(x >> 16);
 }
 
+// ---- attention key horizon -------------------------------------------
+// kv_len: optional int32[B] of per-sequence key counts; keys >= the
+// horizon take no part in attention. nullptr = all S keys. Entries are
+// clamped to [1, S], so a bad length can never index out of bounds.
+DEVINL int kv_horizon(const int* __restrict__ kv_len, long b, int S) {
+  return kv_len ? min(max(kv_len[b], 1), S) : S;
+}
+
 // ---- wave-level reductions (64 lanes) --------------------------------
 DEVINL float wave_sum(float v) {
 #pragma unroll

@@ -4,7 +4,8 @@ from .activation import (GELU, LinearGelu, Softmax, gelu, bias_gelu,
                          softmax)
 from .dropout import Dropout, dropout
 from .dropout_ln import DropoutAddLayerNorm, dropout_add_layer_norm
-from .attention import (AttentionCore, AttentionCoreQKV, attention, attention_qkv)
+from .attention import (AttentionCore, AttentionCoreQKV, attention,
+                        attention_qkv, kv_len_from_mask)
 from .losses import CrossEntropyLoss, cross_entropy
 from .mlm_head import sparse_mlm_head_loss
 from .optim import FusedAdam, FusedSGD, FusedLAMB, clip_grad_norm_
@@ -22,6 +23,7 @@ __all__ = [
     "Dropout", "dropout",
     "DropoutAddLayerNorm", "dropout_add_layer_norm",
     "AttentionCore", "AttentionCoreQKV", "attention", "attention_qkv",
+    "kv_len_from_mask",
     "CrossEntropyLoss", "cross_entropy", "sparse_mlm_head_loss",
     "FusedAdam", "FusedSGD", "FusedLAMB", "clip_grad_norm_",
     "FusedBatchNorm2d", "Linear", "Conv1x1", "conv2d_mfma",
