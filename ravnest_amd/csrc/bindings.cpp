@@ -22,7 +22,7 @@ std::vector<at::Tensor> batchnorm_fwd(at::Tensor x, at::Tensor w,
                                       double momentum, double eps);
 std::vector<at::Tensor> batchnorm_bwd(at::Tensor dy, at::Tensor x,
                                       at::Tensor w, at::Tensor mean,
-                                      at::Tensor rstd);
+                                      at::Tensor rstd, bool training);
 at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
                       c10::optional<at::Tensor> bias, long st, long pad,
                       bool relu);

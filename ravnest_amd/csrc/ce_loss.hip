@@ -53,7 +53,8 @@ DEVINL float row_lse(const T* __restrict__ lr, int V, float* scratch_m,
       if (vmax > m) {
         s = s * __expf(m - vmax) + ls;
         m = vmax;
-      } else {
+      } else if (vmax != -INFINITY) {
+        // a group of eight -inf (padded vocabulary) has ls = NaN: skip it
         s += ls * __expf(vmax - m);
       }
     }
@@ -62,7 +63,7 @@ DEVINL float row_lse(const T* __restrict__ lr, int V, float* scratch_m,
       if (v > m) {
         s = s * __expf(m - v) + 1.f;
         m = v;
-      } else {
+      } else if (v != -INFINITY) {  // -inf - -inf would be NaN
         s += __expf(v - m);
       }
     }
@@ -72,7 +73,7 @@ DEVINL float row_lse(const T* __restrict__ lr, int V, float* scratch_m,
       if (v > m) {
         s = s * __expf(m - v) + 1.f;
         m = v;
-      } else {
+      } else if (v != -INFINITY) {  // -inf - -inf would be NaN
         s += __expf(v - m);
       }
     }

@@ -55,7 +55,7 @@ __global__ void emb2_fwd_kernel(const long* __restrict__ ids,
   // up to 2 bf16x8 vectors per lane covers H <= 1024; generic loop above
   float v[2][8];
   int nvec = 0;
-  float sum = 0.f, sumsq = 0.f;
+  float sum = 0.f;
   for (int base = lane * 8; base < H && nvec < 2; base += WAVE * 8, ++nvec) {
     bf16x8 a = *reinterpret_cast<const bf16x8*>(wr + base);
     bf16x8 p = *reinterpret_cast<const bf16x8*>(pr + base);
@@ -64,7 +64,6 @@ __global__ void emb2_fwd_kernel(const long* __restrict__ ids,
       const float f = us2f((unsigned short)a[j]) + us2f((unsigned short)p[j]);
       v[nvec][j] = f;
       sum += f;
-      sumsq += f * f;
     }
   }
   if (!LN) {
@@ -77,10 +76,21 @@ __global__ void emb2_fwd_kernel(const long* __restrict__ ids,
     }
     return;
   }
-  sum = wave_sum(sum);
-  sumsq = wave_sum(sumsq);
-  const float mean = sum / H;
-  const float var = sumsq / H - mean * mean;
+  // two-pass variance over the registers (free: the row is held anyway).
+  // E[x^2] - mean^2 cancels for rows with a large common offset and can
+  // go negative, which at BERT's eps = 1e-12 means rsqrtf(< 0) = NaN
+  const float mean = wave_sum(sum) / H;
+  float sq = 0.f;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (k >= nvec) break;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = v[k][j] - mean;
+      sq += d * d;
+    }
+  }
+  const float var = wave_sum(sq) / H;
   const float rstd = rsqrtf(var + eps);
   if (lane == 0) {
     mean_out[row] = mean;

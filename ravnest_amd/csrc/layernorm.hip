@@ -4,6 +4,12 @@
 // (bf16x8) when the hidden size allows (guide: scalar bf16 loads are
 // ~2x slower). dgamma/dbeta use a column-parallel reduction kernel
 // (coalesced across lanes) instead of atomics.
+//
+// Row statistics are sums of d = x - K and d^2 with K the row's first
+// element (shifted sums): var = E[d^2] - E[d]^2 then cancels a few bits at
+// most, where E[x^2] - E[x]^2 loses all of them once |mean| / std reaches
+// ~2^12 and goes negative beyond (an fp32 residual stream with a large
+// common offset). One extra broadcast load, no extra pass over the row.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -41,6 +47,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
   const T* xr = x + row * H;
   T* yr = y + row * H;
 
+  const float K = load1(xr);  // shift of the sums, see the header
   float s = 0.f, s2 = 0.f;
   if constexpr (sizeof(T) == 2) {
     if ((H & 7) == 0) {
@@ -49,15 +56,15 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
         bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + g * 8);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          float f = us2f((unsigned short)v[j]);
-          s += f;
-          s2 += f * f;
+          float d = us2f((unsigned short)v[j]) - K;
+          s += d;
+          s2 += d * d;
         }
       }
-      s = wave_sum(s);
-      s2 = wave_sum(s2);
-      const float mean = s / H;
-      const float var = fmaxf(s2 / H - mean * mean, 0.f);
+      s = wave_sum(s) / H;
+      s2 = wave_sum(s2) / H;
+      const float mean = K + s;
+      const float var = fmaxf(s2 - s * s, 0.f);
       const float rstd = rsqrtf(var + eps);
       if (lane == 0) {
         mean_out[row] = mean;
@@ -80,14 +87,14 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
   }
   // generic path
   for (int i = lane; i < H; i += WAVE) {
-    float f = load1(xr + i);
-    s += f;
-    s2 += f * f;
+    float d = load1(xr + i) - K;
+    s += d;
+    s2 += d * d;
   }
-  s = wave_sum(s);
-  s2 = wave_sum(s2);
-  const float mean = s / H;
-  const float var = fmaxf(s2 / H - mean * mean, 0.f);
+  s = wave_sum(s) / H;
+  s2 = wave_sum(s2) / H;
+  const float mean = K + s;
+  const float var = fmaxf(s2 - s * s, 0.f);
   const float rstd = rsqrtf(var + eps);
   if (lane == 0) {
     mean_out[row] = mean;
@@ -121,6 +128,8 @@ __global__ void ln_add_fwd_kernel(const T* __restrict__ a,
   T* yr = y + row * H;
   T* sr = s_out + row * H;
 
+  // shift of the sums: the first element's sum (unrounded is as good)
+  const float K = load1(ar) + load1(br);
   float s1 = 0.f, s2 = 0.f;
   if constexpr (sizeof(T) == 2) {
     if ((H & 7) == 0) {
@@ -134,15 +143,16 @@ __global__ void ln_add_fwd_kernel(const T* __restrict__ a,
           float f = us2f((unsigned short)va[j]) + us2f((unsigned short)vb[j]);
           vs[j] = (short)f2us(f);
           f = us2f((unsigned short)vs[j]);  // quantized sum (bitwise saved)
-          s1 += f;
-          s2 += f * f;
+          const float d = f - K;
+          s1 += d;
+          s2 += d * d;
         }
         *reinterpret_cast<bf16x8*>(sr + g * 8) = vs;
       }
-      s1 = wave_sum(s1);
-      s2 = wave_sum(s2);
-      const float mean = s1 / H;
-      const float var = fmaxf(s2 / H - mean * mean, 0.f);
+      s1 = wave_sum(s1) / H;
+      s2 = wave_sum(s2) / H;
+      const float mean = K + s1;
+      const float var = fmaxf(s2 - s1 * s1, 0.f);
       const float rstd = rsqrtf(var + eps);
       if (lane == 0) {
         mean_out[row] = mean;
@@ -165,14 +175,14 @@ __global__ void ln_add_fwd_kernel(const T* __restrict__ a,
   for (int i = lane; i < H; i += WAVE) {
     float f = load1(ar + i) + load1(br + i);
     store1(sr + i, f);
-    f = load1(sr + i);
-    s1 += f;
-    s2 += f * f;
+    const float d = load1(sr + i) - K;
+    s1 += d;
+    s2 += d * d;
   }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  const float mean = s1 / H;
-  const float var = fmaxf(s2 / H - mean * mean, 0.f);
+  s1 = wave_sum(s1) / H;
+  s2 = wave_sum(s2) / H;
+  const float mean = K + s1;
+  const float var = fmaxf(s2 - s1 * s1, 0.f);
   const float rstd = rsqrtf(var + eps);
   if (lane == 0) {
     mean_out[row] = mean;
@@ -298,6 +308,12 @@ __global__ void ln_bwd_dwdb_partial(const T* __restrict__ dy,
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w,
                                       at::Tensor b, double eps) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous());
+  TORCH_CHECK(x.scalar_type() == at::kFloat ||
+                  x.scalar_type() == at::kBFloat16,
+              "layernorm_fwd: x must be float32 or bfloat16, got ",
+              x.scalar_type());
+  TORCH_CHECK(b.scalar_type() == w.scalar_type(),
+              "layernorm_fwd: weight and bias dtypes differ");
   const int H = x.size(-1);
   const long N = x.numel() / H;
   auto y = at::empty_like(x);
@@ -392,6 +408,12 @@ std::vector<at::Tensor> layernorm_add_fwd(at::Tensor a, at::Tensor b,
                                           double eps) {
   TORCH_CHECK(a.is_cuda() && a.is_contiguous() && b.is_contiguous());
   TORCH_CHECK(a.sizes() == b.sizes() && a.scalar_type() == b.scalar_type());
+  TORCH_CHECK(a.scalar_type() == at::kFloat ||
+                  a.scalar_type() == at::kBFloat16,
+              "layernorm_add_fwd: a must be float32 or bfloat16, got ",
+              a.scalar_type());
+  TORCH_CHECK(bias.scalar_type() == w.scalar_type(),
+              "layernorm_add_fwd: weight and bias dtypes differ");
   const int H = a.size(-1);
   const long N = a.numel() / H;
   auto y = at::empty_like(a);

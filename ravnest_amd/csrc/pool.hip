@@ -51,7 +51,10 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x,
       const int w = w0 + kw;
       if (w < 0 || w >= W) continue;
       const float v = load1(xp + h * W + w);
-      if (v > best) {
+      // torch semantics: NaN wins the max (a diverged activation must not
+      // be laundered), and the first in-bounds element seeds the index so
+      // an all -inf window still routes its gradient somewhere
+      if (bi < 0 || v > best || v != v) {
         best = v;
         bi = h * W + w;
       }

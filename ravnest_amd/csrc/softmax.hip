@@ -40,7 +40,9 @@ __global__ void softmax_fwd_kernel(const T* __restrict__ x,
     if (v > m) {
       s = s * __expf(m - v) + 1.f;
       m = v;
-    } else {
+    } else if (v != -INFINITY) {
+      // a -inf element adds nothing; while m is still -inf (masked
+      // logits at the head of the lane's columns) v - m would be NaN
       s += __expf(v - m);
     }
   }

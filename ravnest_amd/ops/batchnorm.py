@@ -1,9 +1,11 @@
 """Fused BatchNorm2d (NCHW) on CDNA4.
 
 Reference workload parity: BatchNorm in CNN/ResNet/Inception (SURVEY.md
-section 2.3 "standalone BN fwd/bwd with Welford"). GPU path:
-csrc/batchnorm.hip (per-channel block reductions, fp32 stats); CPU path:
-torch native. Drop-in state-dict compatible with nn.BatchNorm2d.
+section 2.3 standalone BN fwd/bwd row). GPU path: csrc/batchnorm.hip
+(per-channel block reductions, fp32 statistics from one read of x as sums
+shifted by the channel's first element, not Welford); CPU path: torch
+native. In eval mode the backward is dx = dy * w * rstd (frozen-BN
+fine-tuning). Drop-in state-dict compatible with nn.BatchNorm2d.
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ class _BatchNormFn(torch.autograd.Function):
                                           running_mean, running_var,
                                           training, momentum, eps)
         ctx.save_for_backward(x, w, mean, rstd)
+        ctx.training = training
         return y
 
     @staticmethod
@@ -30,7 +33,7 @@ class _BatchNormFn(torch.autograd.Function):
         x, w, mean, rstd = ctx.saved_tensors
         ext = get_ext(required=True)
         dx, dw, db = ext.batchnorm_bwd(dy.contiguous(), x, w.float(), mean,
-                                       rstd)
+                                       rstd, ctx.training)
         return dx, dw.to(w.dtype), db.to(w.dtype), None, None, None, None, \
             None
 

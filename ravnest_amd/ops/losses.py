@@ -36,12 +36,22 @@ class _CrossEntropyFn(torch.autograd.Function):
 def cross_entropy(logits: torch.Tensor, targets: torch.Tensor,
                   ignore_index: int = -100) -> torch.Tensor:
     """Mean CE over non-ignored targets. logits (N, V) any float dtype,
-    targets (N,) int64."""
+    targets (N,) int64.
+
+    Logits of -inf (a padded vocabulary, top-k filtered scores) take no
+    part: they add nothing to the loss and get exactly zero gradient, as
+    long as each row keeps one finite logit. A batch whose targets are all
+    `ignore_index` has loss 0 and an all-zero gradient (the mean divides
+    by max(n_valid, 1)), where torch returns NaN."""
     logits2 = logits.reshape(-1, logits.shape[-1])
     targets2 = targets.reshape(-1)
     if logits.is_cuda:
         return _CrossEntropyFn.apply(logits2.contiguous(),
                                      targets2.contiguous(), ignore_index)
+    if not bool((targets2 != ignore_index).any()):
+        lf = logits2.float()
+        return (torch.where(torch.isfinite(lf), lf, torch.zeros_like(lf))
+                * 0.0).sum()
     return torch.nn.functional.cross_entropy(
         logits2.float(), targets2, ignore_index=ignore_index)
 
