@@ -35,6 +35,11 @@ std::vector<at::Tensor> gemm_nt_bf16(at::Tensor A2, at::Tensor B,
                                      c10::optional<at::Tensor> bias,
                                      int64_t epi);
 at::Tensor gemm_wgrad_bf16(at::Tensor dy, at::Tensor x);
+void gemm_nt_bf16_rows(at::Tensor A2, at::Tensor B,
+                       c10::optional<at::Tensor> bias, int64_t epi,
+                       at::Tensor C, at::Tensor row_limit);
+at::Tensor gemm_wgrad_bf16_rows(at::Tensor dy, at::Tensor x,
+                                at::Tensor row_bound);
 at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
                    at::Tensor ws);
 at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
@@ -165,6 +170,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("epi") = 0);
   m.def("gemm_wgrad_bf16", &gemm_wgrad_bf16,
         "split-K wgrad dW = dy^T @ x (tr16 transpose reads, fp32 atomics)");
+  m.def("gemm_nt_bf16_rows", &gemm_nt_bf16_rows,
+        "gemm_nt_bf16 into the caller's C (row stride C.size(1)), rows "
+        "below a device-side int32 limit only; epi 0 or 1",
+        py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("epi"),
+        py::arg("c"), py::arg("row_limit"));
+  m.def("gemm_wgrad_bf16_rows", &gemm_wgrad_bf16_rows,
+        "gemm_wgrad_bf16 over rows [0, round_up(min(*row_bound, M), 64))",
+        py::arg("dy"), py::arg("x"), py::arg("row_bound"));
   m.def("mx_quant", &mx_quant,
         "bf16 -> MX fp8 (e4m3 + per-32 e8m0 scales)");
   m.def("mx_gemm", &mx_gemm, "MX fp8 GEMM: x @ W^T, 32x32x64 scaled MFMA");

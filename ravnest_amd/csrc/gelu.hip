@@ -16,10 +16,15 @@ template <>
 DEVINL float load_pt<bf16_t>(const bf16_t* p) { return bf2f(*p); }
 
 // tanh via the fast hardware exp (libm tanhf is a long VALU chain;
-// these kernels are otherwise HBM-bound)
+// these kernels are otherwise HBM-bound). Written as 1 - 2/(t+1), not
+// (t-1)/(t+1): exp(2x) overflows to inf from x = 44.4 (a pre-activation
+// of 10.06), where the quotient is inf/inf = NaN and this form is
+// 1 - 2/inf = 1; t underflowing to 0 gives -1 in both. The reciprocal is
+// the hardware v_rcp_f32 (1 ulp; rcp(inf) = 0, rcp(1) = 1): an IEEE
+// division expands to ~10 VALU ops per element.
 DEVINL float fast_tanh(float x) {
   const float t = __expf(2.f * x);
-  return (t - 1.f) / (t + 1.f);
+  return 1.f - 2.f * __builtin_amdgcn_rcpf(t + 1.f);
 }
 
 DEVINL float gelu_f(float x) {
@@ -43,7 +48,9 @@ __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
   const long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x);
   const long stride = (long)gridDim.x * blockDim.x;
   if constexpr (sizeof(T) == 2) {
-    const long nv = n >> 3;
+    // vectors of 8 only when H % 8 == 0 (then they never straddle a row
+    // end and n % 8 == 0); any other H takes the scalar loop below
+    const long nv = (H & 7) ? 0 : n >> 3;
     for (long i = i0; i < nv; i += stride) {
       bf16x8 v = *reinterpret_cast<const bf16x8*>(x + i * 8);
       const int hb = (int)((i * 8) % H);  // H%8==0: the 8 never wrap
@@ -55,7 +62,7 @@ __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
       }
       *reinterpret_cast<bf16x8*>(y + i * 8) = o;
     }
-    // tail
+    // H % 8 != 0: everything
     for (long i = nv * 8 + i0; i < n; i += stride)
       y[i] = f2bf(gelu_f(bf2f(x[i]) + load_pt(bias + i % H)));
   } else {
@@ -74,7 +81,7 @@ __global__ void bias_gelu_bwd_kernel(const T* __restrict__ dy,
   const long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x);
   const long stride = (long)gridDim.x * blockDim.x;
   if constexpr (sizeof(T) == 2) {
-    const long nv = n >> 3;
+    const long nv = (H & 7) ? 0 : n >> 3;  // as in the forward
     for (long i = i0; i < nv; i += stride) {
       bf16x8 v = *reinterpret_cast<const bf16x8*>(x + i * 8);
       bf16x8 g = *reinterpret_cast<const bf16x8*>(dy + i * 8);
@@ -170,10 +177,29 @@ static int grid_for(long work, int block) {
   return (int)std::min<long>(g, 2048);
 }
 
+// x: bf16 or fp32, contiguous; bias: fp32, or bf16 next to a bf16 x, of
+// length x.size(-1). The launches below pick a kernel by these two dtypes
+// alone, so anything else has to stop here.
+static void check_bias_gelu(const at::Tensor& x, const at::Tensor& bias,
+                            const char* who) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 1, who,
+              ": x must be a contiguous GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 ||
+                  x.scalar_type() == at::kFloat,
+              who, ": x must be bf16 or fp32");
+  TORCH_CHECK(bias.is_cuda() && bias.is_contiguous(), who,
+              ": bias must be a contiguous GPU tensor");
+  TORCH_CHECK(bias.scalar_type() == at::kFloat ||
+                  (bias.scalar_type() == at::kBFloat16 &&
+                   x.scalar_type() == at::kBFloat16),
+              who, ": bias must be fp32, or bf16 with a bf16 x");
+  TORCH_CHECK(bias.numel() >= 1 && x.size(-1) == bias.numel(), who,
+              ": bias size mismatch");
+}
+
 at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
+  check_bias_gelu(x, bias, "bias_gelu_fwd");
   const int H = bias.numel();
-  TORCH_CHECK(x.size(-1) == H, "bias size mismatch");
   const long n = x.numel();
   auto y = at::empty_like(x);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
@@ -199,7 +225,11 @@ at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
 }
 
 at::Tensor bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && x.is_contiguous());
+  check_bias_gelu(x, bias, "bias_gelu_bwd");
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
+                  dy.scalar_type() == x.scalar_type() &&
+                  dy.sizes() == x.sizes(),
+              "bias_gelu_bwd: dy must match x in dtype and shape");
   const int H = bias.numel();
   const long n = x.numel();
   auto dx = at::empty_like(x);
@@ -230,11 +260,13 @@ at::Tensor bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias) {
 
 std::vector<at::Tensor> bias_gelu_bwd_db(at::Tensor dy, at::Tensor x,
                                          at::Tensor bias) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && x.is_contiguous());
+  check_bias_gelu(x, bias, "bias_gelu_bwd_db");
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
+                  dy.sizes() == x.sizes(),
+              "bias_gelu_bwd_db: dy must match x in shape");
   TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
               x.scalar_type() == at::kBFloat16);
   const int H = (int)bias.numel();
-  TORCH_CHECK(x.size(-1) == H);
   const long N = x.numel() / H;
   auto dx = at::empty_like(dy);
   auto db = at::zeros({H}, x.options().dtype(at::kFloat));

@@ -61,7 +61,10 @@ constexpr int BUF_BYTES = 2 * TILE_BYTES;         // A+B per buffer
 
 DEVINL float gelu_f(float x) {
   const float k = 0.7978845608028654f;  // sqrt(2/pi)
-  const float t = __expf(2.f * k * (x + 0.044715f * x * x * x));
+  // exponent clamped from above: past it t/(t+1) rounds to 1 anyway, and
+  // unclamped t overflows to inf from x = 9.96, where inf/inf is NaN
+  const float t =
+      __expf(fminf(2.f * k * (x + 0.044715f * x * x * x), 30.f));
   return x * t / (t + 1.f);  // 0.5*x*(1+tanh(.)) rewritten in one exp
 }
 
@@ -316,6 +319,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(
   // ONE divergence test for the whole tile, then unpredicated stores.
   const long mRow0 = mBase + wm * 128 + l15;
   const long nCol0 = nBase + (long)j * BN + wn * 64 + ((lane >> 4) << 2);
+  const bool odd_ld = ldc & 1;
   auto epilogue = [&](auto interior) {
 #pragma unroll
     for (int mf = 0; mf < 8; ++mf) {
@@ -329,12 +333,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(
         bool full = true;
         if constexpr (!interior.value) {
           if (n >= N) continue;
-          full = (n + 4 <= N);
+          // n % 4 == 0, so the 8 B row access is 4 B aligned unless ldc
+          // and m are both odd: those rows store element by element
+          full = (n + 4 <= N) && !(odd_ld && (m & 1));
         }
         float v0 = acc[mf][nf][0], v1 = acc[mf][nf][1];
         float v2 = acc[mf][nf][2], v3 = acc[mf][nf][3];
         if (EPI >= 1) {
-          if (full) {
+          // bias + n is 8 B aligned whatever ldc is
+          if (interior.value || n + 4 <= N) {
             const u16x4 bb = *reinterpret_cast<const u16x4*>(bias + n);
             v0 += us2f(bb[0]); v1 += us2f(bb[1]);
             v2 += us2f(bb[2]); v3 += us2f(bb[3]);
@@ -365,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(
       }
     }
   };
-  if (mRow0 + 7 * 16 < M && nCol0 + 3 * 16 + 4 <= N)
+  if (mRow0 + 7 * 16 < M && nCol0 + 3 * 16 + 4 <= N && !odd_ld)
     epilogue(std::true_type{});
   else
     epilogue(std::false_type{});

@@ -280,6 +280,9 @@ static at::Tensor launch_wgrad(const at::Tensor& dy, const at::Tensor& x,
   TORCH_CHECK(M % BM == 0 && M >= 2 * BM,
               "gemm_wgrad: M % 64 == 0 and M >= 128 required");
   TORCH_CHECK(N >= 8 && K >= 8);
+  // the 16 B staging loads (registers and LDS-DMA) need 4 B aligned rows
+  TORCH_CHECK(N % 2 == 0 && K % 2 == 0,
+              "gemm_wgrad: N and K must be even");
   auto ws = at::zeros({N, K}, dy.options().dtype(at::kFloat));
   const int NT = (int)((N + BN - 1) / BN), KT = (int)((K + BK - 1) / BK);
   const long mTiles = M / BM;

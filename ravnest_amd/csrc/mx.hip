@@ -33,8 +33,10 @@ namespace {
 
 // float -> OCP e4m3fn byte, round-to-nearest-even, saturate to ±448
 DEVINL unsigned char f32_to_e4m3(float v) {
-  if (v != v) return 0x7F;  // NaN
   const unsigned int bits = __float_as_uint(v);
+  // NaN and +-inf -> NaN: e4m3fn has no infinity, and saturating one to
+  // 448 would hand the GEMM a finite value
+  if ((bits & 0x7F800000u) == 0x7F800000u) return 0x7F;
   const unsigned char sign = (bits >> 24) & 0x80;
   float a = fabsf(v);
   if (a > 448.f) return sign | 0x7E;  // saturate to max finite
@@ -56,9 +58,9 @@ DEVINL unsigned char f32_to_e4m3(float v) {
       return sign | 0x7E;  // overflow -> max finite (0x7E = 448)
     return sign | (unsigned char)((exp << 3) | mant);
   }
-  // subnormal: value = mant * 2^-9
+  // subnormal: value = mant * 2^-9; a < 2^-6 here, so mant <= 8, and 8
+  // is the encoding 0x08 of the smallest normal 2^-6
   mant = (unsigned int)rintf(a * 512.f);
-  if (mant > 7) mant = 7;
   return sign | (unsigned char)mant;
 }
 
@@ -73,20 +75,23 @@ __global__ void mx_quant_kernel(const bf16_t* __restrict__ x,
   if (blk >= nblocks) return;
   const bf16_t* xp = x + blk * 32;
   const float v = bf2f(xp[e]);
+  // amax over the block's FINITE elements: NaN and +-inf encode as 0x7F
+  // below and leave the scale to the rest of the block
   float amax = fabsf(v);
+  if (!(amax <= 3.3895314e38f)) amax = 0.f;  // bf16 max; false for NaN
 #pragma unroll
   for (int off = 16; off > 0; off >>= 1)
     amax = fmaxf(amax, __shfl_xor(amax, off, WAVE));
-  // e8m0 scale 2^s with amax/2^s <= 448
-  int s = 0;
+  // e8m0 scale 2^s, s = floor(log2(amax / 448)) + 1 clamped to
+  // [-127, 127]: the scaled amax lands in [224, 448). Read off the bits:
+  // amax = 1.m * 2^(E-127) and 448 = 1.75 * 2^8, so the floor is E - 135
+  // when 1.m >= 1.75 and E - 136 below (subnormal amax: E = 0, clamped).
+  int s = -127;
   if (amax > 0.f) {
-    int ex;
-    frexpf(amax / 448.f, &ex);  // amax/448 in [2^(ex-1), 2^ex)
-    s = ex;                      // smallest s with amax/2^s <= 448
+    const unsigned int ab = __float_as_uint(amax);
+    s = (int)(ab >> 23) - 135 + ((ab & 0x7FFFFFu) >= 0x600000u ? 1 : 0);
     if (s < -127) s = -127;
     if (s > 127) s = 127;
-  } else {
-    s = -127;
   }
   q[blk * 32 + e] = f32_to_e4m3(ldexpf(v, -s));
   if (e == 0) scales[blk] = (unsigned char)(s + 127);
@@ -236,12 +241,25 @@ std::vector<at::Tensor> mx_quant(at::Tensor x) {
 at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
                    at::Tensor ws) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte &&
-              w.scalar_type() == at::kByte);
+                  x.is_contiguous() && x.dim() >= 1,
+              "mx_gemm: x must be a contiguous uint8 (e4m3) GPU tensor");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kByte &&
+                  w.is_contiguous() && w.dim() == 2,
+              "mx_gemm: w must be a contiguous 2-d uint8 (e4m3) GPU tensor");
   const int K = (int)x.size(-1);
+  TORCH_CHECK((int)w.size(1) == K && K % 64 == 0 && K >= 64,
+              "mx_gemm: K must match and be a multiple of 64");
   const int M = (int)(x.numel() / K);
   const int N = (int)w.size(0);
-  TORCH_CHECK((int)w.size(1) == K && K % 64 == 0,
-              "mx_gemm: K must match and be a multiple of 64");
+  TORCH_CHECK(M >= 1 && N >= 1);
+  TORCH_CHECK(xs.is_cuda() && ws.is_cuda() &&
+                  xs.scalar_type() == at::kByte &&
+                  ws.scalar_type() == at::kByte,
+              "mx_gemm: scales must be uint8 (e8m0) GPU tensors");
+  TORCH_CHECK(xs.is_contiguous() && ws.is_contiguous() &&
+                  xs.numel() == (long)M * (K / 32) &&
+                  ws.numel() == (long)N * (K / 32),
+              "mx_gemm: scales must be contiguous (rows, K/32)");
   auto y = at::empty({(long)M, (long)N},
                      x.options().dtype(at::kBFloat16));
   const long tiles = (long)((M + 127) / 128) * ((N + 63) / 64);

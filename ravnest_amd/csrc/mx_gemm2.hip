@@ -344,7 +344,9 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
                       f2us(acc[mf][nf][4 * qd + 1]),
                       f2us(acc[mf][nf][4 * qd + 2]),
                       f2us(acc[mf][nf][4 * qd + 3])};
-        if (n + 4 <= N) {
+        // n % 4 == 0: the 8 B store is 4 B aligned unless N and m are
+        // both odd; those rows store element by element
+        if (n + 4 <= N && !((N & 1) && (m & 1))) {
           *reinterpret_cast<u16x4*>(C + m * N + n) = o;
         } else {
           for (int v = 0; v < 4; ++v)
@@ -362,16 +364,27 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
 at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
                     at::Tensor ws) {
   TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kByte &&
-              xq.is_contiguous() && wq.scalar_type() == at::kByte &&
-              wq.is_contiguous());
+                  xq.is_contiguous() && xq.dim() >= 1,
+              "mx_gemm2: xq must be a contiguous uint8 (e4m3) GPU tensor");
+  TORCH_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte &&
+                  wq.is_contiguous() && wq.dim() == 2,
+              "mx_gemm2: wq must be a contiguous 2-d uint8 (e4m3) GPU "
+              "tensor");
   const long K = xq.size(-1);
-  const long M = xq.numel() / K, N = wq.size(0);
   TORCH_CHECK(wq.size(1) == K, "mx_gemm2: K mismatch");
   TORCH_CHECK(K % BKE == 0 && K >= 2 * BKE,
               "mx_gemm2: K % 128 == 0 and K >= 256 required");
-  TORCH_CHECK(xq.numel() < (1ll << 32) && wq.numel() < (1ll << 32));
+  const long M = xq.numel() / K, N = wq.size(0);
+  TORCH_CHECK(M >= 1 && N >= 1, "mx_gemm2: empty operand");
+  TORCH_CHECK(xq.numel() < (1ll << 32) && wq.numel() < (1ll << 32),
+              "mx_gemm2: operands must be < 4 GiB (32-bit staging offsets)");
+  TORCH_CHECK(xs.is_cuda() && ws.is_cuda() &&
+                  xs.scalar_type() == at::kByte &&
+                  ws.scalar_type() == at::kByte,
+              "mx_gemm2: scales must be uint8 (e8m0) GPU tensors");
   TORCH_CHECK(xs.is_contiguous() && ws.is_contiguous() &&
-              xs.numel() == M * (K / 32) && ws.numel() == N * (K / 32));
+                  xs.numel() == M * (K / 32) && ws.numel() == N * (K / 32),
+              "mx_gemm2: scales must be contiguous (rows, K/32)");
   auto C = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
   const int MT = (int)((M + BM - 1) / BM), NT = (int)((N + BN - 1) / BN);
   int tpb = 1;

@@ -40,14 +40,20 @@ def _hand_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
             and x.numel() * 2 < 2**32 and w.numel() * 2 < 2**32)
 
 
+def _hand_wgrad_ok(M: int, N: int, K: int) -> bool:
+    """Shapes gemm_wgrad_bf16 accepts (M % 64 == 0, M >= 128, N and K
+    even and >= 8: its 16-byte staging loads need 4-byte-aligned rows)
+    and wins (N*K <= 2304*768)."""
+    return (M % 64 == 0 and M >= 128 and N >= 8 and K >= 8
+            and N % 2 == 0 and K % 2 == 0 and N * K <= 2304 * 768)
+
+
 def _hand_wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     """dW = dy^T @ x via the split-K tr16 kernel where it measured
     faster than the library (profiles/r02_gemm_vs_blaslt.txt: wins the
     N*K <= 2304*768 shapes, loses the wide ones)."""
     M, N = dy2.shape
-    K = x2.shape[1]
-    if (M % 64 == 0 and M >= 128 and N >= 8 and K >= 8
-            and N * K <= 2304 * 768):
+    if _hand_wgrad_ok(M, N, x2.shape[1]):
         ext = get_ext(required=True)
         return ext.gemm_wgrad_bf16(dy2, x2).to(dy2.dtype)
     return dy2.t() @ x2
