@@ -23,6 +23,15 @@ std::vector<at::Tensor> batchnorm_fwd(at::Tensor x, at::Tensor w,
 std::vector<at::Tensor> batchnorm_bwd(at::Tensor dy, at::Tensor x,
                                       at::Tensor w, at::Tensor mean,
                                       at::Tensor rstd, bool training);
+std::vector<int64_t> batchnorm_relu_launch_constants();
+std::vector<at::Tensor> batchnorm_relu_fwd(
+    at::Tensor x, c10::optional<at::Tensor> residual, at::Tensor w,
+    at::Tensor b, at::Tensor running_mean, at::Tensor running_var,
+    bool training, double momentum, double eps);
+std::vector<at::Tensor> batchnorm_relu_bwd(at::Tensor dy, at::Tensor x,
+                                           at::Tensor y, at::Tensor w,
+                                           at::Tensor mean, at::Tensor rstd,
+                                           bool training, bool want_dr);
 at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w,
                       c10::optional<at::Tensor> bias, long st, long pad,
                       bool relu);
@@ -147,6 +156,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused bias+GELU bwd with in-pass bias-grad column reduction");
   m.def("batchnorm_fwd", &batchnorm_fwd, "fused BatchNorm2d fwd (NCHW)");
   m.def("batchnorm_bwd", &batchnorm_bwd, "fused BatchNorm2d bwd (NCHW)");
+  m.def("batchnorm_relu_launch_constants", &batchnorm_relu_launch_constants,
+        "(grid cap, block size, bytes per lane) of the BN+ReLU elementwise "
+        "kernels");
+  m.def("batchnorm_relu_fwd", &batchnorm_relu_fwd,
+        "fused BatchNorm2d + [residual add] + ReLU fwd (NCHW)", py::arg("x"),
+        py::arg("residual"), py::arg("w"), py::arg("b"),
+        py::arg("running_mean"), py::arg("running_var"),
+        py::arg("training"), py::arg("momentum"), py::arg("eps"));
+  m.def("batchnorm_relu_bwd", &batchnorm_relu_bwd,
+        "fused BatchNorm2d + [residual add] + ReLU bwd: dx, dw, db[, dr]");
   m.def("dropout_fwd", &dropout_fwd, "philox dropout fwd (replayable)",
         py::arg("x"), py::arg("p"), py::arg("seed"),
         py::arg("seed_buf") = py::none());

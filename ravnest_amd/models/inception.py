@@ -10,9 +10,8 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from ..ops import Conv1x1, FusedBatchNorm2d
+from ..ops import Conv1x1, FusedBatchNormReLU2d
 from ..ops import (MaxPool2d as KMaxPool2d, AvgPool2d as KAvgPool2d,
                    AdaptiveAvgPool2d as KAdaptiveAvgPool2d)
 
@@ -25,10 +24,10 @@ class BasicConv2d(nn.Module):
             self.conv = Conv1x1(in_ch, out_ch)
         else:
             self.conv = nn.Conv2d(in_ch, out_ch, bias=False, **kw)
-        self.bn = FusedBatchNorm2d(out_ch, eps=0.001)
+        self.bn = FusedBatchNormReLU2d(out_ch, eps=0.001)
 
     def forward(self, x):
-        return F.relu(self.bn(self.conv(x)), inplace=True)
+        return self.bn(self.conv(x))
 
 
 class InceptionA(nn.Module):

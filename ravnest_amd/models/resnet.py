@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import (AdaptiveAvgPool2d, Conv1x1, FusedBatchNorm2d,
-                   MaxPool2d)
+                   FusedBatchNormAddReLU2d, FusedBatchNormReLU2d, MaxPool2d)
 
 
 class Bottleneck(nn.Module):
@@ -25,23 +25,23 @@ class Bottleneck(nn.Module):
     def __init__(self, in_ch, ch, stride=1, downsample=None):
         super().__init__()
         self.conv1 = Conv1x1(in_ch, ch)
-        self.bn1 = FusedBatchNorm2d(ch)
+        self.bn1 = FusedBatchNormReLU2d(ch)
         self.conv2 = nn.Conv2d(ch, ch, 3, stride=stride, padding=1,
                                bias=False)
-        self.bn2 = FusedBatchNorm2d(ch)
+        self.bn2 = FusedBatchNormReLU2d(ch)
         self.conv3 = Conv1x1(ch, ch * self.expansion)
-        self.bn3 = FusedBatchNorm2d(ch * self.expansion)
-        self.relu = nn.ReLU(inplace=True)
+        # the block tail: relu(bn3(.) + identity) in one module
+        self.bn3 = FusedBatchNormAddReLU2d(ch * self.expansion)
         self.downsample = downsample
 
     def forward(self, x):
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
+        out = self.bn1(self.conv1(x))
+        out = self.bn2(self.conv2(out))
+        out = self.conv3(out)
         if self.downsample is not None:
             identity = self.downsample(x)
-        return self.relu(out + identity)
+        return self.bn3(out, identity)
 
 
 class ResNet(nn.Module):
@@ -49,8 +49,7 @@ class ResNet(nn.Module):
         super().__init__()
         self.in_planes = 64
         self.conv1 = nn.Conv2d(in_ch, 64, 7, stride=2, padding=3, bias=False)
-        self.bn1 = FusedBatchNorm2d(64)
-        self.relu = nn.ReLU(inplace=True)
+        self.bn1 = FusedBatchNormReLU2d(64)
         self.maxpool = MaxPool2d(3, stride=2, padding=1)
         self.layer1 = self._make_layer(64, layers[0])
         self.layer2 = self._make_layer(128, layers[1], stride=2)
@@ -81,7 +80,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(self.bn1(self.conv1(x)))
         x = self.layer1(x)
         x = self.layer2(x)
         x = self.layer3(x)

@@ -9,7 +9,8 @@ from .attention import (AttentionCore, AttentionCoreQKV, attention,
 from .losses import CrossEntropyLoss, cross_entropy
 from .mlm_head import sparse_mlm_head_loss
 from .optim import FusedAdam, FusedSGD, FusedLAMB, clip_grad_norm_
-from .batchnorm import FusedBatchNorm2d
+from .batchnorm import (FusedBatchNorm2d, FusedBatchNormReLU2d,
+                        FusedBatchNormAddReLU2d)
 from .linear import Linear
 from .conv import Conv1x1, conv2d_mfma
 from .embedding import embedding_ln, embedding_add
@@ -26,7 +27,8 @@ __all__ = [
     "kv_len_from_mask",
     "CrossEntropyLoss", "cross_entropy", "sparse_mlm_head_loss",
     "FusedAdam", "FusedSGD", "FusedLAMB", "clip_grad_norm_",
-    "FusedBatchNorm2d", "Linear", "Conv1x1", "conv2d_mfma",
+    "FusedBatchNorm2d", "FusedBatchNormReLU2d", "FusedBatchNormAddReLU2d",
+    "Linear", "Conv1x1", "conv2d_mfma",
     "embedding_ln", "embedding_add",
     "MaxPool2d", "AvgPool2d", "AdaptiveAvgPool2d",
     "MXLinear", "mx_linear",
