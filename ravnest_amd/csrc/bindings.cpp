@@ -11,7 +11,10 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,
 std::vector<at::Tensor> layernorm_add_fwd(at::Tensor a, at::Tensor b,
                                           at::Tensor w, at::Tensor bias,
                                           double eps);
+std::vector<at::Tensor> layernorm_mx_fwd(at::Tensor x, at::Tensor w,
+                                         at::Tensor b, double eps);
 at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias);
+std::vector<at::Tensor> bias_gelu_mx_fwd(at::Tensor x, at::Tensor bias);
 at::Tensor bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias);
 at::Tensor colsum_bf16(at::Tensor x);
 std::vector<at::Tensor> bias_gelu_bwd_db(at::Tensor dy, at::Tensor x,
@@ -50,9 +53,9 @@ void gemm_nt_bf16_rows(at::Tensor A2, at::Tensor B,
 at::Tensor gemm_wgrad_bf16_rows(at::Tensor dy, at::Tensor x,
                                 at::Tensor row_bound);
 at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
-                   at::Tensor ws);
+                   at::Tensor ws, c10::optional<at::Tensor> bias);
 at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
-                    at::Tensor ws);
+                    at::Tensor ws, c10::optional<at::Tensor> bias);
 at::Tensor mx_scale_probe(at::Tensor a, at::Tensor b, at::Tensor sa,
                           at::Tensor sb);
 at::Tensor softmax_fwd(at::Tensor x);
@@ -149,7 +152,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_bwd", &layernorm_bwd, "fused LayerNorm bwd (CDNA4)");
   m.def("layernorm_add_fwd", &layernorm_add_fwd,
         "fused residual-add + LayerNorm fwd");
+  m.def("layernorm_mx_fwd", &layernorm_mx_fwd,
+        "fused LayerNorm fwd + MX fp8 quantisation of y: y, mean, rstd, q, "
+        "s (bf16 x, hidden % 32 == 0)");
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "fused bias+GELU fwd");
+  m.def("bias_gelu_mx_fwd", &bias_gelu_mx_fwd,
+        "fused bias+GELU fwd + MX fp8 quantisation of y: y, q, s (bf16 x, "
+        "last dim % 32 == 0)");
   m.def("bias_gelu_bwd", &bias_gelu_bwd, "fused bias+GELU bwd");
   m.def("colsum_bf16", &colsum_bf16, "column sum bf16 -> fp32");
   m.def("bias_gelu_bwd_db", &bias_gelu_bwd_db,
@@ -199,9 +208,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dy"), py::arg("x"), py::arg("row_bound"));
   m.def("mx_quant", &mx_quant,
         "bf16 -> MX fp8 (e4m3 + per-32 e8m0 scales)");
-  m.def("mx_gemm", &mx_gemm, "MX fp8 GEMM: x @ W^T, 32x32x64 scaled MFMA");
+  // bias: optional bf16 or fp32 (N,), added in the epilogue as
+  // bf16(float(bf16(acc)) + bias): bit-identical to a separate bf16 add
+  m.def("mx_gemm", &mx_gemm, "MX fp8 GEMM: x @ W^T, 32x32x64 scaled MFMA",
+        py::arg("x"), py::arg("xs"), py::arg("w"), py::arg("ws"),
+        py::arg("bias") = py::none());
   m.def("mx_gemm2", &mx_gemm2,
-        "LDS-staged MX fp8 GEMM (256^2 4-phase, scaled 32x32x64 MFMA)");
+        "LDS-staged MX fp8 GEMM (256^2 4-phase, scaled 32x32x64 MFMA)",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"),
+        py::arg("bias") = py::none());
   m.def("mx_scale_probe", &mx_scale_probe,
         "per-lane scale-byte semantics probe");
   m.def("softmax_fwd", &softmax_fwd, "standalone softmax fwd (last dim)");

@@ -5,6 +5,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -41,10 +42,17 @@ DEVINL float gelu_grad_f(float x) {
   return 0.5f * (1.f + th) + 0.5f * x * sech2 * k * (1.f + 3.f * 0.044715f * x2);
 }
 
-template <typename T, typename PT>
+// MX: also emit the MX fp8 quantisation of the bf16-ROUNDED y (e4m3 bytes
+// q + one e8m0 scale per 32 elements in qs, what mx_quant(y) would return).
+// bf16 x and H % 32 == 0 only (host checked): nv is then a multiple of 4
+// and so are i0 and the stride, so the 4 lanes that share a 32-block take
+// the same trips of the vector loop.
+template <typename T, typename PT, bool MX = false>
 __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
                                      const PT* __restrict__ bias,
-                                     T* __restrict__ y, long n, int H) {
+                                     T* __restrict__ y, long n, int H,
+                                     unsigned char* __restrict__ q = nullptr,
+                                     unsigned char* __restrict__ qs = nullptr) {
   const long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x);
   const long stride = (long)gridDim.x * blockDim.x;
   if constexpr (sizeof(T) == 2) {
@@ -61,6 +69,12 @@ __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
         o[j] = (short)f2us(gelu_f(us2f((unsigned short)v[j]) + b));
       }
       *reinterpret_cast<bf16x8*>(y + i * 8) = o;
+      if constexpr (MX) {
+        float yq[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) yq[j] = us2f((unsigned short)o[j]);
+        mx_quant8(yq, q + i * 8, qs + (i >> 2), threadIdx.x);
+      }
     }
     // H % 8 != 0: everything
     for (long i = nv * 8 + i0; i < n; i += stride)
@@ -222,6 +236,44 @@ at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
   }
   HIP_CHECK_LAST();
   return y;
+}
+
+// bias_gelu_fwd + the MX fp8 quantisation of y: (y, q, s) with y
+// bit-identical to bias_gelu_fwd and (q, s) to mx_quant(y).
+std::vector<at::Tensor> bias_gelu_mx_fwd(at::Tensor x, at::Tensor bias) {
+  check_bias_gelu(x, bias, "bias_gelu_mx_fwd");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16,
+              "bias_gelu_mx_fwd: x must be bf16");
+  const int H = bias.numel();
+  TORCH_CHECK(H % 32 == 0,
+              "bias_gelu_mx_fwd: last dim % 32 == 0 required, got ", H);
+  const long n = x.numel();
+  auto y = at::empty_like(x);
+  auto q = at::empty_like(x, x.options().dtype(at::kByte));
+  auto s = at::empty({n / H, (long)(H / 32)}, x.options().dtype(at::kByte));
+  if (n == 0) return {y, q, s};
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  dim3 block(256);
+  dim3 grid(grid_for(n / 8 + 1, 256));
+  if (bias.scalar_type() == at::kFloat) {
+    hipLaunchKernelGGL((bias_gelu_fwd_kernel<bf16_t, float, true>), grid,
+                       block, 0, stream,
+                       reinterpret_cast<const bf16_t*>(x.data_ptr()),
+                       bias.data_ptr<float>(),
+                       reinterpret_cast<bf16_t*>(y.data_ptr()), n, H,
+                       q.data_ptr<unsigned char>(),
+                       s.data_ptr<unsigned char>());
+  } else {
+    hipLaunchKernelGGL((bias_gelu_fwd_kernel<bf16_t, bf16_t, true>), grid,
+                       block, 0, stream,
+                       reinterpret_cast<const bf16_t*>(x.data_ptr()),
+                       reinterpret_cast<const bf16_t*>(bias.data_ptr()),
+                       reinterpret_cast<bf16_t*>(y.data_ptr()), n, H,
+                       q.data_ptr<unsigned char>(),
+                       s.data_ptr<unsigned char>());
+  }
+  HIP_CHECK_LAST();
+  return {y, q, s};
 }
 
 at::Tensor bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias) {

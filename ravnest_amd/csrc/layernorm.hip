@@ -14,6 +14,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -32,14 +33,22 @@ template <>
 DEVINL void store1<float>(float* p, float v) { *p = v; }
 
 // ---------------- forward ----------------
-template <typename T, typename PT>
+// MX: also emit the MX fp8 quantisation of the bf16-ROUNDED y (e4m3 bytes
+// q (N, H) + e8m0 scales qs (N, H/32), what mx_quant(y) would return) from
+// the registers that hold the row. bf16 x and H % 32 == 0 only (host
+// checked): the group count G is then a multiple of 4, so the 4 lanes
+// that share a 32-block enter the second loop's trips together. The same
+// source computes y, mean and rstd in both instantiations.
+template <typename T, typename PT, bool MX = false>
 __global__ void ln_fwd_kernel(const T* __restrict__ x,
                               const PT* __restrict__ w,
                               const PT* __restrict__ b,
                               T* __restrict__ y,
                               float* __restrict__ mean_out,
                               float* __restrict__ rstd_out,
-                              int H, long N, float eps) {
+                              int H, long N, float eps,
+                              unsigned char* __restrict__ q = nullptr,
+                              unsigned char* __restrict__ qs = nullptr) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const long row = (long)blockIdx.x * (blockDim.x / WAVE) + wid;
@@ -81,6 +90,13 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
           o[j] = (short)f2us((f - mean) * rstd * wj + bj);
         }
         *reinterpret_cast<bf16x8*>(yr + g * 8) = o;
+        if constexpr (MX) {
+          float yq[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) yq[j] = us2f((unsigned short)o[j]);
+          mx_quant8(yq, q + row * H + g * 8, qs + row * (H >> 5) + (g >> 2),
+                    lane);
+        }
       }
       return;
     }
@@ -344,6 +360,57 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w,
   }
   HIP_CHECK_LAST();
   return {y, mean, rstd};
+}
+
+// layernorm_fwd + the MX fp8 quantisation of y: (y, mean, rstd, q, s) with
+// y, mean, rstd bit-identical to layernorm_fwd and (q, s) to mx_quant(y).
+std::vector<at::Tensor> layernorm_mx_fwd(at::Tensor x, at::Tensor w,
+                                         at::Tensor b, double eps) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 1);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16,
+              "layernorm_mx_fwd: x must be bfloat16, got ", x.scalar_type());
+  TORCH_CHECK(w.is_cuda() && b.is_cuda() && w.is_contiguous() &&
+                  b.is_contiguous(),
+              "layernorm_mx_fwd: weight and bias must be contiguous GPU "
+              "tensors");
+  TORCH_CHECK(b.scalar_type() == w.scalar_type() &&
+                  (w.scalar_type() == at::kFloat ||
+                   w.scalar_type() == at::kBFloat16),
+              "layernorm_mx_fwd: weight and bias must both be fp32 or bf16");
+  const int H = x.size(-1);
+  TORCH_CHECK(H >= 32 && H % 32 == 0,
+              "layernorm_mx_fwd: hidden size % 32 == 0 required, got ", H);
+  TORCH_CHECK(w.numel() == H && b.numel() == H,
+              "layernorm_mx_fwd: weight/bias size mismatch");
+  const long N = x.numel() / H;
+  auto y = at::empty_like(x);
+  auto mean = at::empty({N}, x.options().dtype(at::kFloat));
+  auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
+  auto q = at::empty_like(x, x.options().dtype(at::kByte));
+  auto s = at::empty({N, (long)(H / 32)}, x.options().dtype(at::kByte));
+  if (N == 0) return {y, mean, rstd, q, s};
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int waves_per_block = 4;
+  dim3 block(WAVE * waves_per_block);
+  dim3 grid((N + waves_per_block - 1) / waves_per_block);
+
+#define DISPATCH_LN_MX_FWD(PT)                                              \
+  hipLaunchKernelGGL((ln_fwd_kernel<bf16_t, PT, true>), grid, block, 0,     \
+                     stream, reinterpret_cast<const bf16_t*>(x.data_ptr()), \
+                     reinterpret_cast<const PT*>(w.data_ptr()),             \
+                     reinterpret_cast<const PT*>(b.data_ptr()),             \
+                     reinterpret_cast<bf16_t*>(y.data_ptr()),               \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(), H, N,  \
+                     (float)eps, q.data_ptr<unsigned char>(),               \
+                     s.data_ptr<unsigned char>())
+
+  if (w.scalar_type() == at::kFloat) {
+    DISPATCH_LN_MX_FWD(float);
+  } else {
+    DISPATCH_LN_MX_FWD(bf16_t);
+  }
+  HIP_CHECK_LAST();
+  return {y, mean, rstd, q, s};
 }
 
 std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,

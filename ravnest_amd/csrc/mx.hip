@@ -24,77 +24,39 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <type_traits>
+
 #include "common.h"
+#include "mx_quant.h"
 
 typedef int i32x8v __attribute__((ext_vector_type(8)));
 typedef float f32x16v __attribute__((ext_vector_type(16)));
 
 namespace {
 
-// float -> OCP e4m3fn byte, round-to-nearest-even, saturate to ±448
-DEVINL unsigned char f32_to_e4m3(float v) {
-  const unsigned int bits = __float_as_uint(v);
-  // NaN and +-inf -> NaN: e4m3fn has no infinity, and saturating one to
-  // 448 would hand the GEMM a finite value
-  if ((bits & 0x7F800000u) == 0x7F800000u) return 0x7F;
-  const unsigned char sign = (bits >> 24) & 0x80;
-  float a = fabsf(v);
-  if (a > 448.f) return sign | 0x7E;  // saturate to max finite
-  if (a < 0.0009765625f)  // < 2^-10 = half of the min subnormal
-    return sign;
-  // scale into e4m3: exponent bias 7, 3 mantissa bits
-  int e;
-  float m = frexpf(a, &e);  // a = m * 2^e, m in [0.5, 1)
-  int exp = e - 1 + 7;      // e4m3 biased exponent of a
-  unsigned int mant;
-  if (exp >= 1) {
-    // normal: mant from m in [1,2)
-    mant = (unsigned int)rintf((m * 2.f - 1.f) * 8.f);
-    if (mant == 8) {
-      mant = 0;
-      exp += 1;
-    }
-    if (exp > 15 || (exp == 15 && mant == 7))
-      return sign | 0x7E;  // overflow -> max finite (0x7E = 448)
-    return sign | (unsigned char)((exp << 3) | mant);
-  }
-  // subnormal: value = mant * 2^-9; a < 2^-6 here, so mant <= 8, and 8
-  // is the encoding 0x08 of the smallest normal 2^-6
-  mant = (unsigned int)rintf(a * 512.f);
-  return sign | (unsigned char)mant;
-}
-
-// bf16 (R, K) -> e4m3 bytes (R, K) + e8m0 scales (R, K/32).
-// one wave per 2 blocks: lane handles 1 elem of a 32-block per half.
+// bf16 (R, K) -> e4m3 bytes (R, K) + e8m0 scales (R, K/32) on the shared
+// block quantiser (mx_quant.h): one lane per 8 consecutive elements, a
+// 16-byte load in and an 8-byte store out. ngroups = R * K / 8 is a
+// multiple of 4 and a quad starts at a multiple of 4, so the early return
+// takes whole quads. ALIGNED = false (a view whose storage offset leaves
+// the base off 16 bytes) loads element by element.
+template <bool ALIGNED>
 __global__ void mx_quant_kernel(const bf16_t* __restrict__ x,
                                 unsigned char* __restrict__ q,
                                 unsigned char* __restrict__ scales,
-                                long nblocks) {
-  const long blk = ((long)blockIdx.x * blockDim.x + threadIdx.x) / 32;
-  const int e = threadIdx.x & 31;
-  if (blk >= nblocks) return;
-  const bf16_t* xp = x + blk * 32;
-  const float v = bf2f(xp[e]);
-  // amax over the block's FINITE elements: NaN and +-inf encode as 0x7F
-  // below and leave the scale to the rest of the block
-  float amax = fabsf(v);
-  if (!(amax <= 3.3895314e38f)) amax = 0.f;  // bf16 max; false for NaN
+                                long ngroups) {
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ngroups) return;
+  float v[8];
+  if constexpr (ALIGNED) {
+    const bf16x8 in = *reinterpret_cast<const bf16x8*>(x + g * 8);
 #pragma unroll
-  for (int off = 16; off > 0; off >>= 1)
-    amax = fmaxf(amax, __shfl_xor(amax, off, WAVE));
-  // e8m0 scale 2^s, s = floor(log2(amax / 448)) + 1 clamped to
-  // [-127, 127]: the scaled amax lands in [224, 448). Read off the bits:
-  // amax = 1.m * 2^(E-127) and 448 = 1.75 * 2^8, so the floor is E - 135
-  // when 1.m >= 1.75 and E - 136 below (subnormal amax: E = 0, clamped).
-  int s = -127;
-  if (amax > 0.f) {
-    const unsigned int ab = __float_as_uint(amax);
-    s = (int)(ab >> 23) - 135 + ((ab & 0x7FFFFFu) >= 0x600000u ? 1 : 0);
-    if (s < -127) s = -127;
-    if (s > 127) s = 127;
+    for (int j = 0; j < 8; ++j) v[j] = us2f((unsigned short)in[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = bf2f(x[g * 8 + j]);
   }
-  q[blk * 32 + e] = f32_to_e4m3(ldexpf(v, -s));
-  if (e == 0) scales[blk] = (unsigned char)(s + 127);
+  mx_quant8(v, q + g * 8, scales + (g >> 2), threadIdx.x);
 }
 
 // y[M,N] (bf16) = x[M,K]e4m3 @ W[N,K]e4m3^T, both with (.., K/32) e8m0
@@ -103,6 +65,9 @@ __global__ void mx_quant_kernel(const bf16_t* __restrict__ x,
 // arithmetic intensity of a 32x32 tile. K streamed from L2; the LDS/
 // 8-phase ladder is the round-2 upgrade.
 typedef int i32x4v __attribute__((ext_vector_type(4)));
+
+DEVINL float mx_bias_at(const float* b, int i) { return b[i]; }
+DEVINL float mx_bias_at(const bf16_t* b, int i) { return bf2f(b[i]); }
 
 DEVINL i32x8v load_frag_ilv(const unsigned char* p, int hi) {
   // k-interleaved fragment halves (see header comment): positions
@@ -115,10 +80,14 @@ DEVINL i32x8v load_frag_ilv(const unsigned char* p, int hi) {
   return f;
 }
 
+// BT: the epilogue's bias type. void = none; else y = bf16(float(bf16(acc))
+// + bias[col]), the two roundings of a separate bf16 add after the GEMM.
+template <typename BT>
 __global__ __launch_bounds__(256, 1) void mx_gemm_kernel(
     const unsigned char* __restrict__ x, const unsigned char* __restrict__ xs,
     const unsigned char* __restrict__ w, const unsigned char* __restrict__ ws,
-    bf16_t* __restrict__ y, int M, int N, int K) {
+    const BT* __restrict__ bias, bf16_t* __restrict__ y, int M, int N,
+    int K) {
   constexpr int MI = 4, NJ = 2;  // 128x64 per wave: 6 loads, 8 MFMAs
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
@@ -175,6 +144,15 @@ __global__ __launch_bounds__(256, 1) void mx_gemm_kernel(
         acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
             af[i], bf[j], acc[i][j], 0, 0, 0, sa[i], 0, sb[j]);
   }
+  // a lane's columns are the same for every row it stores
+  float bv[NJ] = {};
+  if constexpr (!std::is_void_v<BT>) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int col = n0 + j * 32 + j32;
+      if (col < N) bv[j] = mx_bias_at(bias, col);
+    }
+  }
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -183,7 +161,12 @@ __global__ __launch_bounds__(256, 1) void mx_gemm_kernel(
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         const int col = n0 + j * 32 + j32;
-        if (row < M && col < N) y[(long)row * N + col] = f2bf(acc[i][j][r]);
+        if (row < M && col < N) {
+          bf16_t o = f2bf(acc[i][j][r]);
+          if constexpr (!std::is_void_v<BT>)
+            o = f2bf(bf2f(o) + bv[j]);
+          y[(long)row * N + col] = o;
+        }
       }
 }
 
@@ -226,20 +209,27 @@ std::vector<at::Tensor> mx_quant(at::Tensor x) {
   const long R = x.numel() / K;
   auto q = at::empty_like(x, x.options().dtype(at::kByte));
   auto s = at::empty({R, K / 32}, x.options().dtype(at::kByte));
-  const long nblocks = R * (K / 32);
+  const long ngroups = R * (K / 8);
+  if (ngroups == 0) return {q, s};
+  TORCH_CHECK((ngroups + 255) / 256 <= 0x7FFFFFFFl, "mx_quant: too large");
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   dim3 block(256);
-  dim3 grid((unsigned)((nblocks * 32 + 255) / 256));
-  hipLaunchKernelGGL(mx_quant_kernel, grid, block, 0, stream,
-                     reinterpret_cast<const bf16_t*>(x.data_ptr()),
-                     q.data_ptr<unsigned char>(),
-                     s.data_ptr<unsigned char>(), nblocks);
+  dim3 grid((unsigned)((ngroups + 255) / 256));
+  const bf16_t* xp = reinterpret_cast<const bf16_t*>(x.data_ptr());
+  if (reinterpret_cast<uintptr_t>(xp) % 16 == 0)
+    hipLaunchKernelGGL(mx_quant_kernel<true>, grid, block, 0, stream, xp,
+                       q.data_ptr<unsigned char>(),
+                       s.data_ptr<unsigned char>(), ngroups);
+  else
+    hipLaunchKernelGGL(mx_quant_kernel<false>, grid, block, 0, stream, xp,
+                       q.data_ptr<unsigned char>(),
+                       s.data_ptr<unsigned char>(), ngroups);
   HIP_CHECK_LAST();
   return {q, s};
 }
 
 at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
-                   at::Tensor ws) {
+                   at::Tensor ws, c10::optional<at::Tensor> bias) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte &&
                   x.is_contiguous() && x.dim() >= 1,
               "mx_gemm: x must be a contiguous uint8 (e4m3) GPU tensor");
@@ -266,12 +256,28 @@ at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   dim3 block(256);
   dim3 grid((unsigned)((tiles + 3) / 4));
-  hipLaunchKernelGGL(mx_gemm_kernel, grid, block, 0, stream,
-                     x.data_ptr<unsigned char>(),
-                     xs.data_ptr<unsigned char>(),
-                     w.data_ptr<unsigned char>(),
-                     ws.data_ptr<unsigned char>(),
-                     reinterpret_cast<bf16_t*>(y.data_ptr()), M, N, K);
+#define LAUNCH_MX_GEMM(BT, BP)                                              \
+  hipLaunchKernelGGL(mx_gemm_kernel<BT>, grid, block, 0, stream,            \
+                     x.data_ptr<unsigned char>(),                           \
+                     xs.data_ptr<unsigned char>(),                          \
+                     w.data_ptr<unsigned char>(),                           \
+                     ws.data_ptr<unsigned char>(), BP,                      \
+                     reinterpret_cast<bf16_t*>(y.data_ptr()), M, N, K)
+  if (!bias.has_value()) {
+    LAUNCH_MX_GEMM(void, (const void*)nullptr);
+  } else {
+    const at::Tensor& b = *bias;
+    TORCH_CHECK(b.is_cuda() && b.is_contiguous() && b.numel() == N &&
+                    (b.scalar_type() == at::kBFloat16 ||
+                     b.scalar_type() == at::kFloat),
+                "mx_gemm: bias must be a contiguous bf16 or fp32 GPU tensor "
+                "of length N");
+    if (b.scalar_type() == at::kFloat)
+      LAUNCH_MX_GEMM(float, b.data_ptr<float>());
+    else
+      LAUNCH_MX_GEMM(bf16_t, reinterpret_cast<const bf16_t*>(b.data_ptr()));
+  }
+#undef LAUNCH_MX_GEMM
   HIP_CHECK_LAST();
   return y;
 }

@@ -26,6 +26,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 typedef int i32x8v __attribute__((ext_vector_type(8)));
@@ -73,11 +75,42 @@ DEVINL int frag_off8(int rr, int ks, int hi, int pc) {
   return p ^ (((p >> 8) & 7) << 4);
 }
 
+// 4 consecutive bias values from column n as ONE load (n % 4 == 0 and the
+// host hands over a 16-byte-aligned base); a ragged tail loads element by
+// element, columns >= N read as 0 and are never stored. bf16 stays packed:
+// a lane keeps 8 of these across the epilogue.
+template <typename BT> struct BiasVec { using type = f32x4; };
+template <> struct BiasVec<bf16_t> { using type = u16x4; };
+DEVINL f32x4 bias4(const float* b, long n, long N) {
+  if (n + 4 <= N) return *reinterpret_cast<const f32x4*>(b + n);
+  f32x4 r = {0.f, 0.f, 0.f, 0.f};
+  for (int v = 0; v < 4; ++v)
+    if (n + v < N) r[v] = b[n + v];
+  return r;
+}
+DEVINL u16x4 bias4(const bf16_t* b, long n, long N) {
+  const unsigned short* p = reinterpret_cast<const unsigned short*>(b);
+  if (n + 4 <= N) return *reinterpret_cast<const u16x4*>(p + n);
+  u16x4 r = {0, 0, 0, 0};
+  for (int v = 0; v < 4; ++v)
+    if (n + v < N) r[v] = p[n + v];
+  return r;
+}
+DEVINL f32x4 bias4(const void*, long, long) { return {0.f, 0.f, 0.f, 0.f}; }
+DEVINL float bias_val(const f32x4& b, int v) { return b[v]; }
+DEVINL float bias_val(const u16x4& b, int v) { return us2f(b[v]); }
+
+// BT: the epilogue's bias type. void = none; else each output is
+// bf16(float(bf16(acc)) + bias[n]): the two roundings of a separate bf16
+// add after the GEMM, so fusing it changes no bit. The K-loop is the same
+// in every instantiation.
+template <typename BT>
 __global__ __launch_bounds__(512, 2) void mx2_kernel(
     const unsigned char* __restrict__ XQ,
     const unsigned char* __restrict__ XS_T,
     const unsigned char* __restrict__ WQ,
     const unsigned char* __restrict__ WS_T,
+    const BT* __restrict__ bias,
     bf16_t* __restrict__ C, long M, long N, long K, long Mp, long Np,
     int MT, int NTb, int tpb) {
   __shared__ char smem[2 * BUF_FULL];
@@ -330,6 +363,17 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
   // mBase+wm*128+mf*32+l31, N-cols (reg&3)+8*(reg>>2)+4*hi per strip
   const long mRow0 = mBase + wm * 128 + l31;
   const long nCol0 = nBase + (long)j * BN + wn * 64 + 4 * hi;
+  // the lane's 32 columns are the same for its four row fragments: all 8
+  // bias loads go out together, ahead of the first store (loading at each
+  // use would put 32 dependent round trips into the epilogue)
+  typename BiasVec<BT>::type bv[2][4];
+  if constexpr (!std::is_void_v<BT>) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+      for (int qd = 0; qd < 4; ++qd)
+        bv[nf][qd] = bias4(bias, nCol0 + nf * 32 + qd * 8, N);
+  }
 #pragma unroll
   for (int mf = 0; mf < 4; ++mf) {
     const long m = mRow0 + mf * 32;
@@ -340,10 +384,15 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
       for (int qd = 0; qd < 4; ++qd) {
         const long n = nCol0 + nf * 32 + qd * 8;
         if (n >= N) continue;
-        const u16x4 o{f2us(acc[mf][nf][4 * qd + 0]),
-                      f2us(acc[mf][nf][4 * qd + 1]),
-                      f2us(acc[mf][nf][4 * qd + 2]),
-                      f2us(acc[mf][nf][4 * qd + 3])};
+        u16x4 o{f2us(acc[mf][nf][4 * qd + 0]),
+                f2us(acc[mf][nf][4 * qd + 1]),
+                f2us(acc[mf][nf][4 * qd + 2]),
+                f2us(acc[mf][nf][4 * qd + 3])};
+        if constexpr (!std::is_void_v<BT>) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v)
+            o[v] = f2us(us2f(o[v]) + bias_val(bv[nf][qd], v));
+        }
         // n % 4 == 0: the 8 B store is 4 B aligned unless N and m are
         // both odd; those rows store element by element
         if (n + 4 <= N && !((N & 1) && (m & 1))) {
@@ -362,7 +411,7 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
 }  // namespace
 
 at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
-                    at::Tensor ws) {
+                    at::Tensor ws, c10::optional<at::Tensor> bias) {
   TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kByte &&
                   xq.is_contiguous() && xq.dim() >= 1,
               "mx_gemm2: xq must be a contiguous uint8 (e4m3) GPU tensor");
@@ -385,6 +434,17 @@ at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
   TORCH_CHECK(xs.is_contiguous() && ws.is_contiguous() &&
                   xs.numel() == M * (K / 32) && ws.numel() == N * (K / 32),
               "mx_gemm2: scales must be contiguous (rows, K/32)");
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                    bias->numel() == N &&
+                    (bias->scalar_type() == at::kBFloat16 ||
+                     bias->scalar_type() == at::kFloat),
+                "mx_gemm2: bias must be a contiguous bf16 or fp32 GPU "
+                "tensor of length N");
+  // the epilogue loads 4 bias values at a time
+  if (bias.has_value() &&
+      reinterpret_cast<uintptr_t>(bias->data_ptr()) % 16 != 0)
+    bias = bias->clone();
   auto C = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
   const int MT = (int)((M + BM - 1) / BM), NT = (int)((N + BN - 1) / BN);
   int tpb = 1;
@@ -413,13 +473,21 @@ at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
   auto ws_t = pack(ws, N, Np);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   dim3 grid((unsigned)(MT * NTb)), block(512);
-  hipLaunchKernelGGL(mx2_kernel, grid, block, 0, stream,
-                     xq.data_ptr<unsigned char>(),
-                     reinterpret_cast<unsigned char*>(xs_t.data_ptr<int>()),
-                     wq.data_ptr<unsigned char>(),
-                     reinterpret_cast<unsigned char*>(ws_t.data_ptr<int>()),
-                     reinterpret_cast<bf16_t*>(C.data_ptr()), M, N, K, Mp,
-                     Np, MT, NTb, tpb);
+#define LAUNCH_MX2(BT, BP)                                                  \
+  hipLaunchKernelGGL(mx2_kernel<BT>, grid, block, 0, stream,                \
+                     xq.data_ptr<unsigned char>(),                          \
+                     reinterpret_cast<unsigned char*>(xs_t.data_ptr<int>()),\
+                     wq.data_ptr<unsigned char>(),                          \
+                     reinterpret_cast<unsigned char*>(ws_t.data_ptr<int>()),\
+                     BP, reinterpret_cast<bf16_t*>(C.data_ptr()), M, N, K,  \
+                     Mp, Np, MT, NTb, tpb)
+  if (!bias.has_value())
+    LAUNCH_MX2(void, (const void*)nullptr);
+  else if (bias->scalar_type() == at::kFloat)
+    LAUNCH_MX2(float, bias->data_ptr<float>());
+  else
+    LAUNCH_MX2(bf16_t, reinterpret_cast<const bf16_t*>(bias->data_ptr()));
+#undef LAUNCH_MX2
   HIP_CHECK_LAST();
   return C;
 }

@@ -82,13 +82,15 @@ class GPTBlock(nn.Module):
             raise ValueError("fp8 GPT needs n_embd % 64 == 0")
         from ..ops.linear import make_linear
         lin = MXLinear if fp8 else make_linear
-        self.ln1 = FusedLayerNorm(cfg.n_embd)
+        # fp8: ln1 and mlp_in feed an MXLinear and hand it their output
+        # already quantised (ops/mx.py FUSED_QUANT)
+        self.ln1 = FusedLayerNorm(cfg.n_embd, emit_mx=fp8)
         self.qkv = lin(cfg.n_embd, 3 * cfg.n_embd)
         self.core = AttentionCoreQKV(causal=True)
         self.proj = lin(cfg.n_embd, cfg.n_embd)
         self.attn_drop = Dropout(cfg.dropout)
         self.ln2 = FusedLayerNorm(cfg.n_embd)
-        self.mlp_in = LinearGelu(cfg.n_embd, 4 * cfg.n_embd)
+        self.mlp_in = LinearGelu(cfg.n_embd, 4 * cfg.n_embd, emit_mx=fp8)
         self.mlp_out = lin(4 * cfg.n_embd, cfg.n_embd)
         self.mlp_drop = Dropout(cfg.dropout)
 

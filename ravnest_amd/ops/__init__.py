@@ -15,7 +15,7 @@ from .linear import Linear
 from .conv import Conv1x1, conv2d_mfma
 from .embedding import embedding_ln, embedding_add
 from .pool import MaxPool2d, AvgPool2d, AdaptiveAvgPool2d
-from .mx import MXLinear, mx_linear
+from .mx import MXLinear, mx_linear, attach_mx, take_mx
 
 __all__ = [
     "get_ext", "has_ext",
@@ -31,5 +31,5 @@ __all__ = [
     "Linear", "Conv1x1", "conv2d_mfma",
     "embedding_ln", "embedding_add",
     "MaxPool2d", "AvgPool2d", "AdaptiveAvgPool2d",
-    "MXLinear", "mx_linear",
+    "MXLinear", "mx_linear", "attach_mx", "take_mx",
 ]

@@ -13,6 +13,7 @@ import math
 import torch
 import torch.nn as nn
 
+from . import mx as _mx
 from ._ext import get_ext
 
 
@@ -40,6 +41,23 @@ class _BiasGeluFn(torch.autograd.Function):
         dx = ext.bias_gelu_bwd(dy.contiguous(), x, bias)
         db = dx.float().reshape(-1, dx.shape[-1]).sum(0).to(bias.dtype)
         return dx, db
+
+
+class _BiasGeluMXFn(torch.autograd.Function):
+    """bias-GELU that also returns the MX fp8 quantisation (q, s) of its
+    bf16 output, from the same kernel pass. Backward is _BiasGeluFn's."""
+
+    @staticmethod
+    def forward(ctx, x, bias):
+        ext = get_ext(required=True)
+        y, q, s = ext.bias_gelu_mx_fwd(x, bias)
+        ctx.save_for_backward(x, bias)
+        ctx.mark_non_differentiable(q, s)
+        return y, q, s
+
+    @staticmethod
+    def backward(ctx, dy, _dq, _ds):
+        return _BiasGeluFn.backward(ctx, dy)
 
 
 def bias_gelu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -83,17 +101,26 @@ class LinearGelu(nn.Module):
     under RAVNEST_HAND_GEMM=1 (ops/linear.py)."""
     _is_leaf_module = True
 
-    def __init__(self, in_features: int, out_features: int):
+    def __init__(self, in_features: int, out_features: int,
+                 emit_mx: bool = False):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(out_features, in_features))
         self.bias = nn.Parameter(torch.zeros(out_features))
         nn.init.normal_(self.weight, std=0.02)
+        # emit_mx: the output feeds an MXLinear; quantise it in the
+        # bias-GELU kernel and tag the returned tensor (ops.mx.attach_mx)
+        self.emit_mx = emit_mx
 
     def forward(self, x):
         from .linear import _HandLinearGeluFn, _hand_ok, hand_gemm_enabled
         if x.is_cuda and hand_gemm_enabled() and _hand_ok(x, self.weight):
             return _HandLinearGeluFn.apply(x, self.weight, self.bias)
         h = torch.nn.functional.linear(x, self.weight)
+        if self.emit_mx and _mx.FUSED_QUANT and h.is_cuda and \
+                h.dtype == torch.bfloat16 and h.size(-1) % 32 == 0 and \
+                self.bias.dtype in (torch.bfloat16, torch.float32):
+            y, q, s = _BiasGeluMXFn.apply(h.contiguous(), self.bias)
+            return _mx.attach_mx(y, q, s)
         return bias_gelu(h, self.bias)
 
 

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import mx as _mx
 from ._ext import get_ext
 
 
@@ -31,6 +32,23 @@ class _LayerNormFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _LayerNormMXFn(torch.autograd.Function):
+    """LayerNorm that also returns the MX fp8 quantisation (q, s) of its
+    bf16 output, from the same kernel pass. Backward is _LayerNormFn's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        ext = get_ext(required=True)
+        y, mean, rstd, q, s = ext.layernorm_mx_fwd(x, weight, bias, eps)
+        ctx.save_for_backward(x, weight, mean, rstd)
+        ctx.mark_non_differentiable(q, s)
+        return y, q, s
+
+    @staticmethod
+    def backward(ctx, dy, _dq, _ds):
+        return _LayerNormFn.backward(ctx, dy)
+
+
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
                eps: float = 1e-12) -> torch.Tensor:
     if x.is_cuda:
@@ -41,13 +59,22 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
 class FusedLayerNorm(nn.Module):
     _is_leaf_module = True  # fx: custom autograd inside
 
-    def __init__(self, hidden: int, eps: float = 1e-12):
+    def __init__(self, hidden: int, eps: float = 1e-12,
+                 emit_mx: bool = False):
         super().__init__()
         self.weight = nn.Parameter(torch.ones(hidden))
         self.bias = nn.Parameter(torch.zeros(hidden))
         self.eps = eps
+        # emit_mx: the output feeds an MXLinear; quantise it in the same
+        # kernel and tag the returned tensor (ops.mx.attach_mx)
+        self.emit_mx = emit_mx
 
     def forward(self, x):
+        if self.emit_mx and _mx.FUSED_QUANT and x.is_cuda and \
+                x.dtype == torch.bfloat16 and x.size(-1) % 32 == 0:
+            y, q, s = _LayerNormMXFn.apply(x.contiguous(), self.weight,
+                                           self.bias, self.eps)
+            return _mx.attach_mx(y, q, s)
         return layer_norm(x, self.weight, self.bias, self.eps)
 
 
