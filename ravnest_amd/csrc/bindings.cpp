@@ -86,6 +86,9 @@ std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
                                            at::Tensor w, at::Tensor mean,
                                            at::Tensor rstd,
                                            at::Tensor maskbits, double p);
+std::vector<at::Tensor> dropout_add_ln_bwd_dzsum(
+    at::Tensor dy, at::Tensor s, at::Tensor w, at::Tensor mean,
+    at::Tensor rstd, at::Tensor maskbits, double p, bool dzsum_bf16);
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets,
                                int64_t ignore_index);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
@@ -186,6 +189,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed_buf") = py::none());
   m.def("dropout_add_ln_bwd", &dropout_add_ln_bwd,
         "fused dropout + residual add + LayerNorm bwd: dx, dz, dw, db");
+  m.def("dropout_add_ln_bwd_dzsum", &dropout_add_ln_bwd_dzsum,
+        "dropout_add_ln_bwd and dzsum = dz.sum(0), fp32 or bf16: dx, dz, dw, "
+        "db, dzsum");
   m.def("conv2d_fwd", &conv2d_fwd,
         "implicit-GEMM MFMA conv fwd (bf16 NCHW)", py::arg("x"),
         py::arg("w"), py::arg("bias") = py::none(), py::arg("st") = 1,

@@ -245,7 +245,17 @@ __global__ __launch_bounds__(FWD_THREADS) void dropout_add_ln_fwd_kernel(
 // H = 768 needs two registers more than four waves per SIMD allow; the
 // occupancy hint makes the compiler fit them (no scratch, checked with
 // -Rpass-analysis=kernel-resource-usage)
-template <typename PT, int VPL, bool FULL>
+// DZS: also sum the columns of dz, as stored (after the bf16 rounding), into
+// a third slab of the partial row: part is [gridDim.x][3 * H]. That sum is
+// the bias gradient of the Linear that produced z, which autograd would
+// otherwise get from a pass of its own over dz. Twelve more accumulators
+// do not fit at H = 768 (128 VGPRs and 16 bytes of scratch), so up to
+// VPL = 4 every wave keeps its dz sums in an LDS row of its own, behind the
+// 2 * H floats of the final reduction: a lane adds to its own columns with
+// plain 16-byte reads and writes, in row order, so there is no race and
+// the sum is deterministic. VPL = 8 (H > 1024) would need more than 64 KiB
+// of LDS for that and sums in registers.
+template <typename PT, int VPL, bool FULL, bool DZS = false>
 __global__ __launch_bounds__(BWD_THREADS)
 __attribute__((amdgpu_waves_per_eu(VPL <= 3 ? 4 : 1)))
 void dropout_add_ln_bwd_kernel(
@@ -255,7 +265,11 @@ void dropout_add_ln_bwd_kernel(
     const unsigned char* __restrict__ maskbits, bf16_t* __restrict__ dx,
     bf16_t* __restrict__ dz, float* __restrict__ part, int H, long N,
     float scale) {
-  extern __shared__ float red[];  // 2 * H floats
+  extern __shared__ float red[];  // bwd_lds_floats<VPL, DZS>(H)
+  constexpr int NS = DZS ? 3 : 2;
+  constexpr bool ZLDS = DZS && VPL <= 4;  // dz sums in LDS wave rows
+  constexpr bool ZREG = DZS && !ZLDS;     // ... in registers
+  constexpr int ZV = ZREG ? VPL : 1;
   constexpr bool HOIST = VPL <= 4;
   constexpr int PV = HOIST ? VPL : 1;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -277,6 +291,23 @@ void dropout_add_ln_bwd_kernel(
   for (int k = 0; k < VPL; ++k)
 #pragma unroll
     for (int j = 0; j < 4; ++j) accw[k][j] = accb[k][j] = 0.f;
+  float accz[ZV][4];
+  if constexpr (ZREG) {
+#pragma unroll
+    for (int k = 0; k < VPL; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) accz[k][j] = 0.f;
+  }
+  // column c of this wave's dz sums; a lane touches only its own groups
+  float* zrow = red + 2 * H + wid * H;
+  if constexpr (ZLDS) {
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) {
+      const int g = lane + WAVE * k;
+      if (FULL || g < G)
+        *reinterpret_cast<f32x4*>(zrow + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
 
   for (long row = (long)blockIdx.x * wpb + wid; row < N; row += nwaves) {
     const long base = row * H;
@@ -342,7 +373,19 @@ void dropout_add_ln_bwd_kernel(
         for (int j = 0; j < 4; ++j)
           o[j] = ((nib >> j) & 1) ? o[j] * scale : 0.f;
         *reinterpret_cast<u32x2*>(dx + base + 4 * g) = ox;
-        *reinterpret_cast<u32x2*>(dz + base + 4 * g) = pack4(o);
+        const u32x2 oz = pack4(o);
+        *reinterpret_cast<u32x2*>(dz + base + 4 * g) = oz;
+        if constexpr (DZS) unpack4(oz, o);
+        if constexpr (ZREG) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) accz[k][j] += o[j];
+        }
+        if constexpr (ZLDS) {
+          f32x4 zs = *reinterpret_cast<f32x4*>(zrow + 4 * g);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) zs[j] += o[j];
+          *reinterpret_cast<f32x4*>(zrow + 4 * g) = zs;
+        }
       }
     }
   }
@@ -361,9 +404,11 @@ void dropout_add_ln_bwd_kernel(
             if (t == 0) {
               red[c] = accw[k][j];
               red[H + c] = accb[k][j];
+              if constexpr (ZREG) red[2 * H + c] = accz[k][j];
             } else {
               red[c] += accw[k][j];
               red[H + c] += accb[k][j];
+              if constexpr (ZREG) red[2 * H + c] += accz[k][j];
             }
           }
         }
@@ -371,35 +416,49 @@ void dropout_add_ln_bwd_kernel(
     }
     __syncthreads();
   }
-  float* prow = part + (long)blockIdx.x * 2 * H;
-  for (int i = threadIdx.x; i < 2 * H; i += blockDim.x) prow[i] = red[i];
+  float* prow = part + (long)blockIdx.x * NS * H;
+  if constexpr (ZLDS) {
+    // the barrier of the loop above has made every wave's row visible
+    for (int i = threadIdx.x; i < 2 * H; i += blockDim.x) prow[i] = red[i];
+    for (int i = threadIdx.x; i < H; i += blockDim.x) {
+      float t = 0.f;
+      for (int w = 0; w < wpb; ++w) t += red[2 * H + w * H + i];
+      prow[2 * H + i] = t;
+    }
+  } else {
+    for (int i = threadIdx.x; i < NS * H; i += blockDim.x) prow[i] = red[i];
+  }
 }
 
-// sums the per-block partial rows; 32 columns x 32 row slices per block
-template <typename PT>
+// sums the per-block partial rows; 32 columns x 32 row slices per block.
+// ns slabs per partial row: 2, or 3 with the dz column sums, which go to
+// dzs in the dtype ZT of the Linear bias they are the gradient of
+template <typename PT, typename ZT>
 __global__ __launch_bounds__(1024) void dropout_add_ln_bwd_finalize_kernel(
     const float* __restrict__ part, PT* __restrict__ dw, PT* __restrict__ db,
-    int H, int nparts) {
+    ZT* __restrict__ dzs, int H, int nparts, int ns) {
   __shared__ float tile[32][33];
   const int c = threadIdx.x & 31;
   const int sl = threadIdx.x >> 5;
-  const int col = blockIdx.x * 32 + c;  // in [0, 2 * H)
+  const int col = blockIdx.x * 32 + c;  // in [0, ns * H)
   float acc = 0.f;
-  if (col < 2 * H) {
+  if (col < ns * H) {
 #pragma unroll 4
     for (int q = sl; q < nparts; q += 32)
-      acc += part[(long)q * 2 * H + col];
+      acc += part[(long)q * ns * H + col];
   }
   tile[sl][c] = acc;
   __syncthreads();
-  if (sl == 0 && col < 2 * H) {
+  if (sl == 0 && col < ns * H) {
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) t += tile[i][c];
     if (col < H)
       store_p1(dw + col, t);
-    else
+    else if (col < 2 * H)
       store_p1(db + (col - H), t);
+    else
+      store_p1(dzs + (col - 2 * H), t);
   }
 }
 
@@ -425,11 +484,16 @@ int fwd_resident_blocks() {
       dropout_add_ln_fwd_kernel<PT, VPL, FULL>, FWD_THREADS, 0);
   return n;
 }
-template <typename PT, int VPL, bool FULL>
+// floats of dynamic LDS the backward kernel uses (see its DZS comment)
+template <int VPL, bool DZS>
+constexpr size_t bwd_lds_floats(int H) {
+  return (size_t)(!DZS ? 2 : VPL <= 4 ? 2 + BWD_THREADS / WAVE : 3) * H;
+}
+template <typename PT, int VPL, bool FULL, bool DZS>
 int bwd_resident_blocks() {
   static const int n = resident_blocks(
-      dropout_add_ln_bwd_kernel<PT, VPL, FULL>, BWD_THREADS,
-      2 * VPL * 256 * sizeof(float));
+      dropout_add_ln_bwd_kernel<PT, VPL, FULL, DZS>, BWD_THREADS,
+      bwd_lds_floats<VPL, DZS>(VPL * 256) * sizeof(float));
   return n;
 }
 
@@ -526,10 +590,11 @@ std::vector<at::Tensor> dropout_add_ln_fwd(at::Tensor z, at::Tensor a,
   return {y, s_out, mean, rstd, maskbits};
 }
 
-std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
-                                           at::Tensor w, at::Tensor mean,
-                                           at::Tensor rstd,
-                                           at::Tensor maskbits, double p) {
+// zs: 0 = {dx, dz, dw, db}; 1 / 2 = those and the column sums of dz as
+// fp32 / bf16
+static std::vector<at::Tensor> dropout_add_ln_bwd_impl(
+    at::Tensor dy, at::Tensor s, at::Tensor w, at::Tensor mean,
+    at::Tensor rstd, at::Tensor maskbits, double p, int zs) {
   check_common(s, w, "dropout_add_ln_bwd");
   check_common(dy, w, "dropout_add_ln_bwd");
   TORCH_CHECK(dy.sizes() == s.sizes() && aligned8(dy) && aligned8(s));
@@ -546,25 +611,37 @@ std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
   auto dz = at::empty_like(s);
   auto dw = at::empty({H}, w.options());
   auto db = at::empty({H}, w.options());
+  at::Tensor dzs;
+  if (zs)
+    dzs = at::empty({H}, w.options().dtype(zs == 1 ? at::kFloat
+                                                   : at::kBFloat16));
   if (N == 0) {
     dw.zero_();
     db.zero_();
+    if (zs) {
+      dzs.zero_();
+      return {dx, dz, dw, db, dzs};
+    }
     return {dx, dz, dw, db};
   }
   const float scale = 1.0f / (1.0f - (float)p);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const int wpb = BWD_THREADS / WAVE;
-  const size_t lds = 2 * (size_t)H * sizeof(float);
+  const int ns = zs ? 3 : 2;
+  const long want = (N + wpb - 1) / wpb;
+  at::Tensor part;
+  int nparts = 0;
 
-#define DAL_LAUNCH_BWD(PT, VPL, FULL)                                       \
+#define DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, DZS)                             \
   do {                                                                      \
-    const long want = (N + wpb - 1) / wpb;                                  \
-    const int nparts =                                                      \
-        (int)std::min<long>(want, bwd_resident_blocks<PT, VPL, FULL>());    \
-    auto part = at::empty({nparts, 2 * H}, s.options().dtype(at::kFloat));  \
-    hipLaunchKernelGGL((dropout_add_ln_bwd_kernel<PT, VPL, FULL>),          \
+    nparts = (int)std::min<long>(                                           \
+        want, bwd_resident_blocks<PT, VPL, FULL, DZS>());                   \
+    part = at::empty({nparts, ns * H}, s.options().dtype(at::kFloat));      \
+    hipLaunchKernelGGL((dropout_add_ln_bwd_kernel<PT, VPL, FULL, DZS>),     \
                        dim3(nparts),                                        \
-                       dim3(BWD_THREADS), lds, stream,                      \
+                       dim3(BWD_THREADS),                                   \
+                       (bwd_lds_floats<VPL, DZS>(H)) * sizeof(float),       \
+                       stream,                                              \
                        reinterpret_cast<const bf16_t*>(dy.data_ptr()),      \
                        reinterpret_cast<const bf16_t*>(s.data_ptr()),       \
                        reinterpret_cast<const PT*>(w.data_ptr()),           \
@@ -573,11 +650,21 @@ std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
                        reinterpret_cast<bf16_t*>(dx.data_ptr()),            \
                        reinterpret_cast<bf16_t*>(dz.data_ptr()),            \
                        part.data_ptr<float>(), H, N, scale);                \
-    hipLaunchKernelGGL((dropout_add_ln_bwd_finalize_kernel<PT>),            \
-                       dim3((2 * H + 31) / 32), dim3(1024), 0, stream,      \
-                       part.data_ptr<float>(),                              \
-                       reinterpret_cast<PT*>(dw.data_ptr()),                \
-                       reinterpret_cast<PT*>(db.data_ptr()), H, nparts);    \
+  } while (0)
+#define DAL_LAUNCH_BWD_FIN(PT, ZT)                                          \
+  hipLaunchKernelGGL((dropout_add_ln_bwd_finalize_kernel<PT, ZT>),          \
+                     dim3((ns * H + 31) / 32), dim3(1024), 0, stream,       \
+                     part.data_ptr<float>(),                                \
+                     reinterpret_cast<PT*>(dw.data_ptr()),                  \
+                     reinterpret_cast<PT*>(db.data_ptr()),                  \
+                     zs ? reinterpret_cast<ZT*>(dzs.data_ptr()) : nullptr,  \
+                     H, nparts, ns)
+#define DAL_LAUNCH_BWD(PT, VPL, FULL)                                       \
+  do {                                                                      \
+    if (zs) DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, true);                       \
+    else DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, false);                         \
+    if (zs == 2) DAL_LAUNCH_BWD_FIN(PT, bf16_t);                            \
+    else DAL_LAUNCH_BWD_FIN(PT, float);                                     \
   } while (0)
 
   if (w.scalar_type() == at::kFloat)
@@ -585,5 +672,22 @@ std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
   else
     DAL_DISPATCH_VPL(bf16_t, DAL_LAUNCH_BWD);
   HIP_CHECK_LAST();
+  if (zs) return {dx, dz, dw, db, dzs};
   return {dx, dz, dw, db};
+}
+
+std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
+                                           at::Tensor w, at::Tensor mean,
+                                           at::Tensor rstd,
+                                           at::Tensor maskbits, double p) {
+  return dropout_add_ln_bwd_impl(dy, s, w, mean, rstd, maskbits, p, 0);
+}
+
+// dropout_add_ln_bwd and dzsum = dz.sum(0) (fp32 sums of the stored bf16
+// values), returned as fp32 or bf16: {dx, dz, dw, db, dzsum}
+std::vector<at::Tensor> dropout_add_ln_bwd_dzsum(
+    at::Tensor dy, at::Tensor s, at::Tensor w, at::Tensor mean,
+    at::Tensor rstd, at::Tensor maskbits, double p, bool dzsum_bf16) {
+  return dropout_add_ln_bwd_impl(dy, s, w, mean, rstd, maskbits, p,
+                                 dzsum_bf16 ? 2 : 1);
 }

@@ -11,13 +11,29 @@ BERT-base config: L=12, H=768, A=12, I=3072, vocab=30522, seq<=512.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ..ops import embedding_ln
 from ..ops import (AttentionCoreQKV, Dropout, DropoutAddLayerNorm,
                    FusedLayerNorm, GELU, LinearGelu)
 from ..ops.linear import make_linear
+
+
+def _plain_biased_linear(lin) -> bool:
+    return type(lin) is nn.Linear and lin.bias is not None
+
+
+def _linear_bias_downstream(lin, x):
+    """lin(x) with the bias detached: the same addmm runs forward, but
+    autograd's addmm backward no longer reduces the output gradient over
+    its rows for the bias. The caller hands lin.bias to the fused op that
+    consumes the result, whose backward produces that gradient from
+    registers (ops/dropout_ln.py zbias)."""
+    return F.linear(x, lin.weight, lin.bias.detach())
 
 
 class BertConfig:
@@ -93,13 +109,18 @@ class BertSelfAttention(nn.Module):
             causal=False, prob_dropout=cfg.dropout if exact else 0.0)
         self.out = make_linear(cfg.hidden, cfg.hidden)
 
-    def forward(self, x, mask):
+    def forward(self, x, mask, out_bias_downstream: bool = False):
+        """out_bias_downstream: the caller takes the bias gradient of
+        self.out from the op that consumes the result (BertLayer.ln1); the
+        projection then runs with its bias detached."""
         # packed (B,S,3,H,D) qkv: the attention kernel reads the
         # projection's natural layout and returns token-major O — no
         # permute/contiguous copies (unflatten also keeps the fx graph
         # free of .size() scalar nodes)
         qkv = self.qkv(x).unflatten(-1, (3, self.heads, self.head_dim))
         o = self.core(qkv, mask)
+        if out_bias_downstream:
+            return _linear_bias_downstream(self.out, o)
         return self.out(o)
 
 
@@ -115,10 +136,38 @@ class BertLayer(nn.Module):
         self.mlp_out = make_linear(cfg.intermediate, cfg.hidden)
         self.ln2 = DropoutAddLayerNorm(cfg.hidden, cfg.layer_norm_eps,
                                        cfg.dropout)
+        # RAVNEST_FUSED_BIAS_GRAD=0: the attn.out and mlp_out bias gradients
+        # come from autograd's own reduction again (A/B inside one build).
+        # The qkv bias keeps autograd's reduction either way: summing dqkv in
+        # the attention backward kernels measured slower than that reduction
+        # (profiles/bias_grad_gelu.txt, section 2).
+        self.fused_bias_grad = \
+            os.environ.get("RAVNEST_FUSED_BIAS_GRAD", "1") != "0"
+
+    def _bias_downstream(self, ln, a, lin) -> bool:
+        # a plain nn.Linear whose consumer takes the fused kernel path.
+        # Not while fx-tracing (a is a Proxy; torch.is_tensor comes first
+        # because even reading a parameter there adds a node to the graph):
+        # the pipeline splitter may cut between a projection and its
+        # consumer, which would part the bias from its gradient; traced
+        # graphs keep the module calls.
+        return (self.fused_bias_grad and torch.is_tensor(a)
+                and _plain_biased_linear(lin) and ln.takes_zbias(a, lin))
 
     def forward(self, x, mask):
-        x = self.ln1(x, self.attn(x, mask))
-        x = self.ln2(x, self.mlp_out(self.mlp_in(x)))
+        # attn.out -> ln1 and mlp_out -> ln2: the LayerNorm backward sums
+        # dz for the projection's bias (ops/dropout_ln.py zbias)
+        if self._bias_downstream(self.ln1, x, self.attn.out):
+            x = self.ln1(x, self.attn(x, mask, out_bias_downstream=True),
+                         zbias=self.attn.out.bias)
+        else:
+            x = self.ln1(x, self.attn(x, mask))
+        if self._bias_downstream(self.ln2, x, self.mlp_out):
+            x = self.ln2(x, _linear_bias_downstream(self.mlp_out,
+                                                    self.mlp_in(x)),
+                         zbias=self.mlp_out.bias)
+        else:
+            x = self.ln2(x, self.mlp_out(self.mlp_in(x)))
         return x
 
 
