@@ -52,6 +52,8 @@ void gemm_nt_bf16_rows(at::Tensor A2, at::Tensor B,
                        at::Tensor C, at::Tensor row_limit);
 at::Tensor gemm_wgrad_bf16_rows(at::Tensor dy, at::Tensor x,
                                 at::Tensor row_bound);
+std::vector<at::Tensor> gemm_wgrad256_bf16(at::Tensor dy, at::Tensor x,
+                                           bool want_db, bool out_fp32);
 at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
                    at::Tensor ws, c10::optional<at::Tensor> bias);
 at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
@@ -212,6 +214,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_wgrad_bf16_rows", &gemm_wgrad_bf16_rows,
         "gemm_wgrad_bf16 over rows [0, round_up(min(*row_bound, M), 64))",
         py::arg("dy"), py::arg("x"), py::arg("row_bound"));
+  m.def("gemm_wgrad256_bf16", &gemm_wgrad256_bf16,
+        "split-M wgrad on the 256x256 template: [dW bf16 (fp32 if "
+        "out_fp32), db = dy.sum(0) bf16 if want_db]; N, K % 256 == 0, "
+        "M % 64 == 0; no atomics, deterministic",
+        py::arg("dy"), py::arg("x"), py::arg("want_db") = false,
+        py::arg("out_fp32") = false);
   m.def("mx_quant", &mx_quant,
         "bf16 -> MX fp8 (e4m3 + per-32 e8m0 scales)");
   // bias: optional bf16 or fp32 (N,), added in the epilogue as

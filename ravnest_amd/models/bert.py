@@ -20,11 +20,12 @@ import torch.nn.functional as F
 from ..ops import embedding_ln
 from ..ops import (AttentionCoreQKV, Dropout, DropoutAddLayerNorm,
                    FusedLayerNorm, GELU, LinearGelu)
-from ..ops.linear import make_linear
+from ..ops.linear import WgradLinear, make_linear
+from ..ops.linear import linear as _wgrad_linear
 
 
 def _plain_biased_linear(lin) -> bool:
-    return type(lin) is nn.Linear and lin.bias is not None
+    return type(lin) in (nn.Linear, WgradLinear) and lin.bias is not None
 
 
 def _linear_bias_downstream(lin, x):
@@ -32,7 +33,10 @@ def _linear_bias_downstream(lin, x):
     autograd's addmm backward no longer reduces the output gradient over
     its rows for the bias. The caller hands lin.bias to the fused op that
     consumes the result, whose backward produces that gradient from
-    registers (ops/dropout_ln.py zbias)."""
+    registers (ops/dropout_ln.py zbias). The weight gradient takes the
+    route lin itself would (ops/linear.py linear)."""
+    if type(lin) is WgradLinear:
+        return _wgrad_linear(x, lin.weight, lin.bias.detach())
     return F.linear(x, lin.weight, lin.bias.detach())
 
 

@@ -115,7 +115,8 @@ class LinearGelu(nn.Module):
         from .linear import _HandLinearGeluFn, _hand_ok, hand_gemm_enabled
         if x.is_cuda and hand_gemm_enabled() and _hand_ok(x, self.weight):
             return _HandLinearGeluFn.apply(x, self.weight, self.bias)
-        h = torch.nn.functional.linear(x, self.weight)
+        from .linear import linear as _linear  # dW from the wgrad kernel
+        h = _linear(x, self.weight)
         if self.emit_mx and _mx.FUSED_QUANT and h.is_cuda and \
                 h.dtype == torch.bfloat16 and h.size(-1) % 32 == 0 and \
                 self.bias.dtype in (torch.bfloat16, torch.float32):
