@@ -70,8 +70,8 @@ DEVINL void adam_one(float& p, float g, float& m, float& v, float lr,
 }
 
 // vectorized: 4 elements/thread/iter with 16-byte fp32 state accesses
-// (m/v/master are the traffic; chunks are 64Ki elements so the body is
-// always aligned and the tail only exists in the last chunk)
+// (m/v/master are the traffic; chunks are 64Ki elements, so every chunk of
+// a tensor shares its base alignment and the tail only exists in the last)
 template <typename T, bool CLIP>
 __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
                                float b1, float b2, float eps, float wd,
@@ -84,9 +84,12 @@ __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
   // freeze at capture — engine/graphstep.py)
   if (lr_buf) {
     lr = *lr_buf;
+    // 1 - b^step as -expm1(step * log b): no cancellation at small steps
+    // (1 - powf(0.999, 1) alone loses 6e-5 relative), full-precision
+    // functions, once per thread. b = 0 gives -expm1(-inf) = 1.
     const float st = (float)*step_buf;
-    bc1 = 1.f - __powf(b1, st);
-    bc2 = 1.f - __powf(b2, st);
+    bc1 = -expm1f(st * logf(b1));
+    bc2 = -expm1f(st * logf(b2));
   }
   // clip-by-global-norm coefficient (grad_norm_finalize_kernel). CLIP is
   // a template flag, not a runtime branch, so that the no-clip
@@ -94,7 +97,20 @@ __global__ void adam_mt_kernel(const Chunk* __restrict__ chunks, float lr,
   float gs = 1.f;
   if constexpr (CLIP) gs = *gscale;
   const Chunk c = chunks[blockIdx.x];
-  const int n4 = c.n >> 2;
+  // the vector body needs 16-byte aligned fp32 pointers and 8-byte aligned
+  // bf16 ones; a chunk with any other base (a param or grad that is a view
+  // into a larger buffer) takes the scalar loop as a whole
+  const unsigned long long fp32_bits =
+      reinterpret_cast<unsigned long long>(c.m) |
+      reinterpret_cast<unsigned long long>(c.v) |
+      reinterpret_cast<unsigned long long>(c.master);
+  const unsigned long long pg_bits =
+      reinterpret_cast<unsigned long long>(c.p) |
+      reinterpret_cast<unsigned long long>(c.g);
+  const bool aligned = sizeof(T) == 2
+                           ? ((fp32_bits & 15ull) | (pg_bits & 7ull)) == 0
+                           : ((fp32_bits | pg_bits) & 15ull) == 0;
+  const int n4 = aligned ? c.n >> 2 : 0;
   float4* m4 = reinterpret_cast<float4*>(c.m);
   float4* v4 = reinterpret_cast<float4*>(c.v);
   float4* w4 = reinterpret_cast<float4*>(c.master);

@@ -1,7 +1,8 @@
 """Fused multi-tensor optimizers: Adam, SGD+momentum, LAMB.
 
 Reference workload parity: Adam (CNN), SGD+momentum+wd (ResNet/Inception),
-LAMB (BERT, torch_optimizer.Lamb) — SURVEY.md section 2.3 optimizer row.
+LAMB (BERT; the formulation is in FusedLAMB's docstring) — SURVEY.md
+section 2.3 optimizer row.
 GPU path: ONE kernel launch per step applies the update across every
 parameter chunk (csrc/optim.hip, apex-style chunked multi-tensor apply);
 LAMB adds a norm-reduction phase for the per-tensor trust ratio. CPU
@@ -16,6 +17,7 @@ hipGraph. The gradients in memory keep their unclipped values.
 from __future__ import annotations
 
 import math
+import struct
 
 import torch
 from torch.optim import Optimizer
@@ -25,6 +27,11 @@ from ._ext import get_ext
 
 def _on_gpu(params):
     return any(p.is_cuda for p in params)
+
+
+def _f32(x):
+    """A hyperparameter as the kernels receive it: rounded to fp32."""
+    return struct.unpack("f", struct.pack("f", x))[0]
 
 
 def _cpu_clip_stats(grads, max_norm, stats):
@@ -65,6 +72,8 @@ class _FusedOptimizer(Optimizer):
     A subclass supplies
       _collect(group) -> lists (params first, grads second) of the params
                          that have a grad, creating their state,
+      _split(lists) -> those lists cut into parts that one update call
+                         can take (default: one part),
       _table_lists(lists) -> the five lists of ``mt_build_table``,
       _table_fn, the name of its ``fused_*_table`` entry point,
       _update_args(group, lists) -> that call's arguments between the
@@ -112,6 +121,27 @@ class _FusedOptimizer(Optimizer):
         return ([self.state[p]["master"] for p in ps]
                 if ps and ps[0].dtype == torch.bfloat16 else [])
 
+    def _split(self, lists):
+        return [lists]
+
+    # state that stays fp32 whatever the dtype of its parameter
+    _FP32_STATE = ("m", "v", "momentum_buffer", "master")
+
+    def load_state_dict(self, state_dict):
+        """torch's ``load_state_dict`` casts every floating-point state
+        tensor to the dtype of its parameter, which would round the fp32
+        moments and masters of bf16 parameters to bf16. They are put back
+        as fp32 copies of the saved values on the parameter's device."""
+        super().load_state_dict(state_dict)
+        saved = state_dict["state"]
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        ps = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(ids, ps):
+            for k in self._FP32_STATE:
+                if k in saved.get(i, ()):
+                    self.state[p][k] = saved[i][k].detach().to(
+                        device=p.device, dtype=torch.float32, copy=True)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
@@ -119,7 +149,7 @@ class _FusedOptimizer(Optimizer):
         for group in self.param_groups:
             lists = self._collect(group)
             if lists[0]:
-                work.append((group, lists))
+                work.extend((group, part) for part in self._split(lists))
         if not work:
             return loss
         clip = self.max_grad_norm is not None
@@ -188,8 +218,26 @@ class _MomentsOptimizer(_FusedOptimizer):
             vs.append(st["v"])
         return ps, gs, ms, vs
 
+    def _split(self, lists):
+        """One part per step value: the bias corrections are per update
+        call, and a parameter that had no grad for some steps (an unused
+        head, a layer frozen for a while) is behind the others. Normally
+        all steps agree and the group stays one table and one launch."""
+        steps = [self.state[p]["step"] for p in lists[0]]
+        if all(s == steps[0] for s in steps):
+            return [lists]
+        by_step: dict = {}
+        for i, s in enumerate(steps):
+            by_step.setdefault(s, []).append(i)
+        return [tuple([col[i] for i in idx] for col in lists)
+                for idx in by_step.values()]
+
     def _bias_corrections(self, group, ps):
-        b1, b2 = group["betas"]
+        # ps is one part of _split: every parameter in it is at this step.
+        # The betas are the fp32 values the moments are updated with:
+        # 1 - 0.999 and 1 - float32(0.999) differ by 1.3e-5 relative,
+        # which at step 1 would go straight into vhat.
+        b1, b2 = (_f32(b) for b in group["betas"])
         step = self.state[ps[0]]["step"]
         return 1 - b1 ** step, 1 - b2 ** step
 
@@ -311,7 +359,8 @@ class FusedAdam(_MomentsOptimizer):
                 *self._bias_corrections(group, lists[0]))
 
     def _cpu_update(self, group, lists, coef):
-        b1, b2 = group["betas"]
+        # fp32 betas, as on the GPU: 1 - b is then exact in fp32 as well
+        b1, b2 = (_f32(b) for b in group["betas"])
         bc1, bc2 = self._bias_corrections(group, lists[0])
         for p, g, m, v in zip(*lists):
             gf = g.float()
@@ -377,9 +426,19 @@ class FusedSGD(_FusedOptimizer):
 
 
 class FusedLAMB(_MomentsOptimizer):
-    """LAMB (You et al.) with the per-tensor trust ratio
-    clamp(|w| / |update|). Parity: torch_optimizer.Lamb used by the BERT
-    example (examples/bert/provider.py:49-50)."""
+    """LAMB (You et al.), as implemented here, per tensor:
+
+        m = b1*m + (1-b1)*g,  v = b2*v + (1-b2)*g*g   (g after clipping)
+        upd = (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps) + weight_decay*w
+        trust = min(|w| / |upd|, clamp_trust)  if |w| > 0 and |upd| > 0
+                1                              otherwise
+        w -= lr * trust * upd
+
+    with t the step count of that parameter and L2 norms over the whole
+    tensor: the moments are bias-corrected, weight decay is added to the
+    update (not to the gradient), and the clamp bounds the RATIO, not the
+    weight norm. Other LAMB implementations differ in each of these
+    points; this docstring states what tests/optim_cases.py pins."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, clamp_trust=10.0, max_grad_norm=None):
@@ -397,7 +456,8 @@ class FusedLAMB(_MomentsOptimizer):
                 group["clamp_trust"])
 
     def _cpu_update(self, group, lists, coef):
-        b1, b2 = group["betas"]
+        # fp32 betas, as on the GPU: 1 - b is then exact in fp32 as well
+        b1, b2 = (_f32(b) for b in group["betas"])
         bc1, bc2 = self._bias_corrections(group, lists[0])
         for p, g, m, v in zip(*lists):
             gf = g.float()
