@@ -1,4 +1,6 @@
-// Flash-style fused attention BACKWARD for CDNA4 (gfx950), bf16, D=64.
+// Flash-style fused attention BACKWARD for CDNA4 (gfx950), bf16, D=64
+// (the D=128 kernels live in attention_bwd128.hip; attn_bwd_impl below
+// dispatches on D).
 //
 // Three kernels (flash2-style split, no atomics):
 //   attn_bwd_delta: Delta[row] = dO[row] . O[row]            (rowwise)
@@ -18,19 +20,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "attention_kv_len.h"
-#include "common.h"
-
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// hardware transpose read (guide T10; semantics verified by tr16_probe in
-// attention.hip): each lane loads 4 contiguous bf16 at its OWN 8-B
-// address; per 16-lane group the loads form a [4][16] block M (lane
-// order) and lane q receives column q.
-#define DS_TR16(p) __builtin_amdgcn_ds_read_tr16_b64_v4bf16( \
-    (__attribute__((address_space(3))) bf16x4v*)( \
-        (__attribute__((address_space(3))) void*)(p)))
+#include "attention_bwd_common.h"
 
 namespace {
 
@@ -76,15 +66,6 @@ DEVINL unsigned drop_bits_rowfixed(const unsigned* __restrict__ mb,
 }
 
 
-// element offset of (b, h, row) = b*bs + h*hs + row*rs (see attention.hip)
-struct StridesB { long bs, hs, rs; };
-
-DEVINL unsigned int pack_bf2b(float lo, float hi) {
-  return (unsigned int)f2us(lo) | ((unsigned int)f2us(hi) << 16);
-}
-
-// transform a [row-pattern][col=lane] f32 acc (16 regs) into the A-operand
-// fragments covering k=rows: pa[step] holds rows 16*step + (lane>>5)*8+e.
 // per-lane byte offset for a tr16 B-fragment read of
 // B[k = kbase + 0..3][j = hh*32 + (lane&31)] from a 128-B-row LDS image,
 // optionally XOR-swizzled ((row&15)<<4, 16-B granularity — an 8-B-aligned
@@ -100,27 +81,6 @@ DEVINL int tr16_b_off(int lane, int kbase, int hh) {
   return off;
 }
 
-DEVINL void acc_to_afrag(const f32x16& acc, unsigned int pa[2][4]) {
-#pragma unroll
-  for (int step = 0; step < 2; ++step) {
-    const int b0 = step * 8;
-    unsigned int c01 = pack_bf2b(acc[b0 + 0], acc[b0 + 1]);
-    unsigned int c23 = pack_bf2b(acc[b0 + 2], acc[b0 + 3]);
-    unsigned int c45 = pack_bf2b(acc[b0 + 4], acc[b0 + 5]);
-    unsigned int c67 = pack_bf2b(acc[b0 + 6], acc[b0 + 7]);
-    {
-      auto r2 = __builtin_amdgcn_permlane32_swap(c01, c45, false, false);
-      pa[step][0] = r2[0];
-      pa[step][2] = r2[1];
-    }
-    {
-      auto r2 = __builtin_amdgcn_permlane32_swap(c23, c67, false, false);
-      pa[step][1] = r2[0];
-      pa[step][3] = r2[1];
-    }
-  }
-}
-
 // A key block wholly past the sequence's key horizon has P == 0 for every
 // query: its gradient rows are exact zeros. Each wave stores its 32 rows.
 DEVINL void store_zero_rows(bf16_t* __restrict__ gp, int k0, int S,
@@ -133,33 +93,6 @@ DEVINL void store_zero_rows(bf16_t* __restrict__ gp, int k0, int S,
       if (krow < S) gp[(long)krow * rs + hh * 32 + j32] = f2bf(0.f);
     }
   }
-}
-
-// Delta[row] = sum_d dO[row][d] * O[row][d]. D/8 lanes per row, bf16x8
-// loads (the one-wave-per-row 2-B-scalar version measured 7x off the
-// bandwidth bound at 2.5% of the BERT step — rocprofv3 r01 final).
-template <int D>
-__global__ void attn_bwd_delta_kernel(const bf16_t* __restrict__ dout,
-                                      const bf16_t* __restrict__ o,
-                                      float* __restrict__ delta, int S,
-                                      long H, long NR, StridesB sdo) {
-  constexpr int LPR = D / 8;  // lanes per row
-  const int lane = threadIdx.x & (WAVE - 1);
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long id = t / LPR;
-  if (id >= NR) return;
-  const long bh = id / S;
-  const long row = id % S;
-  const long off = (bh / H) * sdo.bs + (bh % H) * sdo.hs + row * sdo.rs +
-                   (t % LPR) * 8;
-  bf16x8v a = *reinterpret_cast<const bf16x8v*>(dout + off);
-  bf16x8v b = *reinterpret_cast<const bf16x8v*>(o + off);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s += (float)a[j] * (float)b[j];
-#pragma unroll
-  for (int m = 1; m < LPR; m <<= 1) s += __shfl_xor(s, m, WAVE);
-  if ((lane & (LPR - 1)) == 0) delta[id] = s;
 }
 
 // -------------------------------------------------------------------
@@ -856,11 +789,21 @@ std::vector<at::Tensor> attn_bwd_impl(
     const bf16_t* dob, at::Tensor lse, const float* mask_ptr, bool has_mask,
     bool causal, double scale, long B, long H, int S, StridesB sio,
     StridesB sdo, StridesB sg, bf16_t* dqb, bf16_t* dkb, bf16_t* dvb,
-    const at::TensorOptions& fopt, const int* kvl, float pdrop = 0.f,
-    const unsigned* mbits = nullptr) {
+    const at::TensorOptions& fopt, const int* kvl, int D,
+    float pdrop = 0.f, const unsigned* mbits = nullptr) {
   const float inv_keep = 1.f / (1.f - pdrop);
   auto delta = at::empty({B * H * (long)S}, fopt);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (D == 128) {
+    TORCH_CHECK(pdrop == 0.f,
+                "attn_bwd: fused prob-dropout is head_dim 64 only");
+    attn_bwd_d128_launch(qb, kb, vb, ob, dob, lse.data_ptr<float>(),
+                         delta.data_ptr<float>(), mask_ptr, causal,
+                         (float)scale, B, H, S, sio, sdo, sg, dqb, dkb, dvb,
+                         kvl, stream);
+    HIP_CHECK_LAST();
+    return {};
+  }
   const long NR = B * H * (long)S;
   hipLaunchKernelGGL((attn_bwd_delta_kernel<64>),
                      dim3((NR * 8 + 255) / 256), dim3(256), 0, stream, dob,
@@ -934,7 +877,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(q.scalar_type() == at::kBFloat16);
   const long B = q.size(0), H = q.size(1);
   const int S = q.size(2), D = q.size(3);
-  TORCH_CHECK(D == 64, "attn_bwd kernel: head_dim 64");
+  TORCH_CHECK(D == 64 || D == 128, "attn_bwd kernel: head_dim 64 or 128");
   auto dc = dout.contiguous();
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
@@ -957,7 +900,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                 reinterpret_cast<bf16_t*>(dq.data_ptr()),
                 reinterpret_cast<bf16_t*>(dk.data_ptr()),
                 reinterpret_cast<bf16_t*>(dv.data_ptr()),
-                q.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B));
+                q.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B), D);
   return {dq, dk, dv};
 }
 
@@ -971,7 +914,8 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3);
   const long B = qkv.size(0), H = qkv.size(3);
   const int S = qkv.size(1), D = qkv.size(4);
-  TORCH_CHECK(D == 64, "attn_bwd_qkv kernel: head_dim 64");
+  TORCH_CHECK(D == 64 || D == 128,
+              "attn_bwd_qkv kernel: head_dim 64 or 128");
   auto dc = dout.contiguous();
   auto dqkv = at::empty_like(qkv);
 
@@ -996,6 +940,6 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                 mask_ptr, has_mask, causal, scale, B, H, S, sp, sod, sp,
                 dbase, dbase + HD, dbase + 2 * HD,
                 qkv.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B),
-                (float)pdrop, mb);
+                D, (float)pdrop, mb);
   return dqkv;
 }

@@ -5,10 +5,13 @@ Reference workload parity: minGPT causal self-attention
 SURVEY.md section 2.3. Forward is the hand-written HIP kernel
 (csrc/attention.hip): per Q-tile online-softmax over K/V tiles, bf16 MFMA
 (32x32x16), XOR-swizzled K LDS tiles, no S x S score matrix in HBM; it
-returns O and the log-sum-exp rows. Backward on the D=64 path runs the
-fused flash backward kernels (csrc/attention_bwd.hip: delta + dv + dk +
-dq, P recomputed from (Q,K,lse) on-chip); other head dims recompute P
-with plain hipBLASLt GEMMs + elementwise torch.
+returns O and the log-sum-exp rows. Backward runs the fused flash
+backward kernels (delta + dv + dk + dq, P recomputed from (Q,K,lse)
+on-chip): csrc/attention_bwd.hip at D=64, csrc/attention_bwd128.hip at
+D=128, separate and packed layouts alike. BWD_D128 off
+(RAVNEST_ATTN_BWD_D128=0) sends D=128 back to the composed backward that
+recomputes P with hipBLASLt GEMMs + elementwise torch and materialises
+(B,H,S,S) tensors; it is kept as the A/B arm of tools/attn_bench.py.
 
 Shapes: q,k,v (B, H, S, D); additive mask broadcastable to (B, 1, S, S)
 or None; causal flag for GPT-style models.
@@ -40,6 +43,10 @@ from ._ext import get_ext
 # Derive the key horizon from the padding mask (module docstring). Read at
 # call time: flip ravnest_amd.ops.attention.KV_SKIP to compare both paths.
 KV_SKIP = os.environ.get("RAVNEST_ATTN_KV_SKIP", "0") == "1"
+
+# D=128 backward through the flash kernels (and the packed layout through
+# _AttnQKVFn). Read at call time; off = the composed backward.
+BWD_D128 = os.environ.get("RAVNEST_ATTN_BWD_D128", "1") != "0"
 
 
 def kv_len_from_mask(mask):
@@ -112,14 +119,16 @@ class _AttnFn(torch.autograd.Function):
         q, k, v, mask, o, lse, kv_len = ctx.saved_tensors
         causal, scale = ctx.causal, ctx.scale
         do = do.contiguous()
-        if q.shape[-1] == 64:
+        D = q.shape[-1]
+        if D == 64 or (D == 128 and BWD_D128):
             ext = get_ext(required=True)
             dq, dk, dv = ext.attn_bwd(
                 q, k, v, o, do, lse,
                 mask if mask is not None else torch.Tensor(), causal, scale,
                 kv_len)
             return dq, dk, dv, None, None, None, None
-        # head_dim != 64: recompute P from lse via library GEMMs
+        # composed arm (D=128 with BWD_D128 off): recompute P from lse via
+        # library GEMMs
         # P = exp(S*scale + mask - lse)
         s = (q @ k.transpose(-2, -1)).float() * scale
         if causal:
@@ -216,13 +225,15 @@ class _AttnQKVFn(torch.autograd.Function):
 def attention_qkv(qkv, mask=None, causal=False, scale=None,
                   prob_dropout=0.0, kv_len=None):
     """qkv (B,S,3,H,D) -> (B,S,H*D). prob_dropout fuses attention-prob
-    dropout into the kernels (D=64 path). kv_len: see the module
-    docstring."""
+    dropout into the kernels (D=64 path). D=128 takes the packed kernels
+    too unless prob_dropout > 0 or BWD_D128 is off. kv_len: see the
+    module docstring."""
     H, D = qkv.shape[-2], qkv.shape[-1]
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     kv_len = _as_kv_len(kv_len, qkv.shape[0], qkv.device)
-    if qkv.is_cuda and D == 64:
+    if qkv.is_cuda and (D == 64 or (D == 128 and BWD_D128
+                                    and prob_dropout == 0)):
         o = _AttnQKVFn.apply(qkv.contiguous(), mask, causal, scale,
                              prob_dropout, kv_len)
         return o.flatten(2)

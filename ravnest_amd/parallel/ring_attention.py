@@ -77,7 +77,8 @@ def _ring_shift(tensors, group, dst, src):
 
 
 def _use_kernel(q):
-    return (q.is_cuda and q.dtype == torch.bfloat16 and q.shape[-1] == 64
+    return (q.is_cuda and q.dtype == torch.bfloat16
+            and q.shape[-1] in (64, 128)
             and get_ext(required=False) is not None)
 
 

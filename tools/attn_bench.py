@@ -11,6 +11,12 @@ only (KV_SKIP off), mask with the key horizon derived on the device
 (KV_SKIP on, derivation launch included), explicit kv_len without mask.
 Medians and min..max spreads per mode; useful FLOPs counted from the
 lengths (every query row against the sequence's live keys).
+
+--D 128: fwd, then the backward on both arms, alternated round after
+round in one process: the flash kernels (BWD_D128 on; separate and packed
+layouts) and the composed torch backward (BWD_D128 off, what
+RAVNEST_ATTN_BWD_D128=0 selects). --causal for the causal case. Medians
+with min..max; TF/s over the 7 matmul passes (halved work when causal).
 """
 import argparse
 import math
@@ -101,6 +107,47 @@ def bench_fill(ext, dev, B, S, H, D, fills, rounds, iters):
             print(f"  {m:13s} " + "  ".join(parts))
 
 
+def bench_d128(ext, dev, B, S, H, D, causal, rounds, iters):
+    import importlib
+    # ops/__init__ exports the attention() function under the same name
+    attn_mod = importlib.import_module("ravnest_amd.ops.attention")
+    scale = 1.0 / math.sqrt(D)
+    empty = torch.Tensor()
+    mm = 2 * B * H * S * S * D * (0.5 if causal else 1.0)
+    q, k, v = (torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16,
+                           requires_grad=True) for _ in range(3))
+    o = attn_mod.attention(q, k, v, causal=causal)   # one graph, both arms
+    do = torch.randn_like(o)
+    qkv = torch.stack([q, k, v], 0).detach().permute(1, 3, 0, 2, 4)
+    qkv = qkv.contiguous()
+    o_p, lse_p = ext.attn_fwd_qkv(qkv, empty, causal, scale)[:2]
+    do_p = do.transpose(1, 2).contiguous()
+
+    def bwd(flag):
+        attn_mod.BWD_D128 = flag
+        return torch.autograd.grad(o, (q, k, v), do, retain_graph=True)
+
+    arms = {
+        "kernel": lambda: bwd(True),
+        "kernel packed": lambda: ext.attn_bwd_qkv(
+            qkv, o_p, do_p, lse_p, empty, causal, scale, 0.0, None, None),
+        "composed": lambda: bwd(False),
+    }
+    t_f = timeit(lambda: ext.attn_fwd(q, k, v, empty, causal, scale), iters)
+    t = {a: [] for a in arms}
+    for _ in range(rounds):
+        for a, fn in arms.items():
+            t[a].append(timeit(fn, iters, 2))
+    attn_mod.BWD_D128 = True
+    print(f"B={B} H={H} S={S} D={D} causal={causal}: fwd {t_f:7.3f} ms "
+          f"({2 * mm / t_f / 1e9:6.1f} TF/s); bwd {rounds} rounds x {iters} "
+          f"iters per arm, arms alternated; ms median [min..max]")
+    for a, x in t.items():
+        med = statistics.median(x)
+        print(f"  bwd {a:13s} {med:8.3f} [{min(x):8.3f}..{max(x):8.3f}] "
+              f"({7 * mm / med / 1e9:6.1f} TF/s)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
@@ -109,6 +156,7 @@ def main():
     ap.add_argument("--D", type=int, default=64)
     ap.add_argument("--fill", type=float, nargs="+", default=None,
                     help="live share(s) of a right-padded batch")
+    ap.add_argument("--causal", action="store_true")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
     args = ap.parse_args()
@@ -120,6 +168,10 @@ def main():
     torch.manual_seed(0)
     if args.fill:
         bench_fill(ext, dev, B, S, H, D, args.fill, args.rounds, args.iters)
+        return
+    if D == 128:
+        bench_d128(ext, dev, B, S, H, D, args.causal, args.rounds,
+                   args.iters)
         return
 
     # FLOPs: fwd 2 matmuls, bwd 7 matmul passes (S,dP twice + dV,dK,dQ)
