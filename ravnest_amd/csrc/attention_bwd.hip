@@ -1,11 +1,13 @@
-// Flash-style fused attention BACKWARD for CDNA4 (gfx950), bf16, D=64
-// (the D=128 kernels live in attention_bwd128.hip; attn_bwd_impl below
-// dispatches on D).
+// Flash-style fused attention BACKWARD for CDNA4 (gfx950), bf16, D=64,
+// on 32-row tiles: the kernels of the fused probability dropout and the
+// RAVNEST_ATTN_BWD64=0 arm. Without dropout D=64 runs the 64-row-stage
+// kernels of attention_bwd64.hip, D=128 those of attention_bwd128.hip;
+// attn_bwd_impl below dispatches.
 //
-// Three kernels (flash2-style split, no atomics):
+// Four kernels (flash2-style split, no atomics):
 //   attn_bwd_delta: Delta[row] = dO[row] . O[row]            (rowwise)
-//   attn_bwd_dkv:   each wave owns a 32-KEY tile, loops Q tiles,
-//                   recomputes P from (Q,K,lse), accumulates dV,dK
+//   attn_bwd_dv/dk: each wave owns a 32-KEY tile, loops Q tiles,
+//                   recomputes P from (Q,K,lse), accumulates dV / dK
 //   attn_bwd_dq:    each wave owns a 32-ROW Q tile, loops KV tiles,
 //                   recomputes P^T, accumulates dQ
 //
@@ -65,21 +67,6 @@ DEVINL unsigned drop_bits_rowfixed(const unsigned* __restrict__ mb,
   return bits;
 }
 
-
-// per-lane byte offset for a tr16 B-fragment read of
-// B[k = kbase + 0..3][j = hh*32 + (lane&31)] from a 128-B-row LDS image,
-// optionally XOR-swizzled ((row&15)<<4, 16-B granularity — an 8-B-aligned
-// read never crosses the flipped boundary). The row-dependent XOR also
-// de-conflicts the 4-lanes-per-row gather (rows r and r+2 land 32 B
-// apart), so the swizzled images need no extra padding.
-template <bool SWZ>
-DEVINL int tr16_b_off(int lane, int kbase, int hh) {
-  const int q4 = lane & 15;
-  const int row = kbase + (q4 >> 2);
-  int off = row * 128 + hh * 64 + ((lane >> 4) & 1) * 32 + 8 * (q4 & 3);
-  if (SWZ) off ^= (row & 15) << 4;
-  return off;
-}
 
 // A key block wholly past the sequence's key horizon has P == 0 for every
 // query: its gradient rows are exact zeros. Each wave stores its 32 rows.
@@ -436,192 +423,6 @@ __global__ __launch_bounds__(256, DROP ? 3 : 4) void attn_bwd_dk_kernel(
 }
 
 // -------------------------------------------------------------------
-// merged dv+dk kernel (A/B LOSER, kept behind RAVNEST_ATTN_MERGED_DKV=1
-// for reference): one S-matmul + one staging feeds both accumulators,
-// but the combined register set lands at 210 VGPRs = 2 waves/SIMD and
-// measures 161 TF vs the split pair's 270 TF — the occupancy tier
-// outweighs the saved matmul pass on this latency-bound structure.
-// -------------------------------------------------------------------
-__global__ __launch_bounds__(256) void attn_bwd_dvdk_kernel(
-    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
-    const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    const float* __restrict__ mask, bf16_t* __restrict__ dk,
-    bf16_t* __restrict__ dv, int S, int causal, float scale, int has_mask,
-    long H, StridesB sio, StridesB sdo, StridesB sg,
-    const int* __restrict__ kv_len) {
-  constexpr int D = 64;
-  __shared__ __attribute__((aligned(16))) char smem[16384 + 16384];
-  float* lse_lds = reinterpret_cast<float*>(smem + 16384);
-  float* dlt_lds = lse_lds + 2048;
-  const int st_row = threadIdx.x >> 3;
-  const int st_c16 = (threadIdx.x & 7) * 16;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int hi = lane >> 5;
-  const int j32 = lane & 31;
-  const int k0 = (blockIdx.x * 4 + (int)(threadIdx.x / WAVE)) * 32;
-  const bool live_wave = k0 < S;
-  const long bh = blockIdx.y;
-  const long b = bh / H, h = bh % H;
-  const bf16_t* qp = q + b * sio.bs + h * sio.hs;
-  const bf16_t* kp = k + b * sio.bs + h * sio.hs;
-  const bf16_t* vp = v + b * sio.bs + h * sio.hs;
-  const bf16_t* dop = dout + b * sdo.bs + h * sdo.hs;
-  bf16_t* dkp = dk + b * sg.bs + h * sg.hs;
-  bf16_t* dvp = dv + b * sg.bs + h * sg.hs;
-  const float* lsep = lse + bh * (long)S;
-  const float* dltp = delta + bh * (long)S;
-  const float* mp = has_mask ? (mask + b * (long)S) : nullptr;
-  // key horizon: block-uniform exit before the first barrier
-  const int L = kv_horizon(kv_len, b, S);
-  if ((int)blockIdx.x * 128 >= L) {
-    if (live_wave) {
-      store_zero_rows(dkp, k0, S, sg.rs, hi, j32);
-      store_zero_rows(dvp, k0, S, sg.rs, hi, j32);
-    }
-    return;
-  }
-  const bool lse_in_lds = S <= 2048;
-  if (lse_in_lds) {
-    for (int i = threadIdx.x; i < S; i += blockDim.x) {
-      lse_lds[i] = lsep[i];
-      dlt_lds[i] = dltp[i];
-    }
-  }
-
-  const int key = k0 + j32;
-  const bf16_t* krp = kp + (long)min(key, S - 1) * sio.rs;
-  const bf16_t* vrp = vp + (long)min(key, S - 1) * sio.rs;
-  bf16x8v kf[4], vf[4];
-  if (live_wave) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      kf[s] = *reinterpret_cast<const bf16x8v*>(krp + s * 16 + hi * 8);
-      vf[s] = *reinterpret_cast<const bf16x8v*>(vrp + s * 16 + hi * 8);
-    }
-  }
-  const float mask_val = (has_mask && key < S) ? mp[min(key, S - 1)] : 0.f;
-
-  f32x16 dv_acc[2], dk_acc[2];
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      dv_acc[hh][r] = 0.f;
-      dk_acc[hh][r] = 0.f;
-    }
-
-  const int q_start = causal ? blockIdx.x * 128 : 0;
-  // glds staging: both tiles are XOR-swizzled images, so both use the
-  // source-side inverse permutation (see the dv kernel's comment)
-  const int wdst = ((int)threadIdx.x >> 6) * 1024;
-  const int p16 = (int)threadIdx.x * 16;
-  const int inv_r7 = ((p16 >> 7) & 1) ^ ((p16 >> 10) & 1);
-  const int p_src = (p16 & ~0xF0) | ((((p16 >> 4) & 1) ^ inv_r7) << 4) |
-                    ((((p16 >> 5) & 1) ^ ((p16 >> 8) & 1)) << 5) |
-                    ((((p16 >> 6) & 1) ^ ((p16 >> 9) & 1)) << 6) |
-                    (inv_r7 << 7);
-  const int s_row = p_src >> 7, s_col = p_src & 127;
-  auto stage2 = [&](int qt, char* sl) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(
-            reinterpret_cast<const char*>(qp) +
-            (long)min(qt + s_row, S - 1) * sio.rs * 2 + s_col),
-        (__attribute__((address_space(3))) void*)(sl + wdst), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(
-            reinterpret_cast<const char*>(dop) +
-            (long)min(qt + s_row, S - 1) * sdo.rs * 2 + s_col),
-        (__attribute__((address_space(3))) void*)(sl + 4096 + wdst),
-        16, 0, 0);
-  };
-  stage2(q_start, smem);
-  for (int q0 = q_start; q0 < S; q0 += 32) {
-    const int slot = ((q0 - q_start) >> 5) & 1;
-    const char* q_lds = smem + slot * 8192;
-    const char* do_lds = q_lds + 4096;
-    __syncthreads();
-    const bool have_next = q0 + 32 < S;
-    if (have_next)  // T14: next tile's LDS-DMA under this compute
-      stage2(q0 + 32, smem + (slot ^ 1) * 8192);
-    const bool compute = live_wave && k0 < L && (!causal || q0 + 31 >= k0);
-    if (compute) {
-      f32x16 s_acc, dp_acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        s_acc[r] = 0.f;
-        dp_acc[r] = 0.f;
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int foff = (j32 * 128 + (s * 16 + hi * 8) * 2) ^
-                         ((j32 & 15) << 4);
-        bf16x8v qf = *reinterpret_cast<const bf16x8v*>(q_lds + foff);
-        bf16x8v dof = *reinterpret_cast<const bf16x8v*>(do_lds + foff);
-        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kf[s], s_acc,
-                                                        0, 0, 0);
-        dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vf[s], dp_acc,
-                                                         0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qrow = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const int qclmp = min(qrow, S - 1);
-        const float l = lse_in_lds ? lse_lds[qclmp] : lsep[qclmp];
-        const float dlt = lse_in_lds ? dlt_lds[qclmp] : dltp[qclmp];
-        float sv = s_acc[r] * scale + mask_val;
-        bool dead = (qrow >= S) || (key >= L) || (causal && key > qrow) ||
-                    !isfinite(l);
-        const float p = dead ? 0.f : __expf(sv - l);
-        s_acc[r] = p;                                          // P
-        dp_acc[r] = dead ? 0.f : p * (dp_acc[r] - dlt) * scale;  // dS
-      }
-      unsigned int pa_p[2][4], pa_ds[2][4];
-      acc_to_afrag(s_acc, pa_p);
-      acc_to_afrag(dp_acc, pa_ds);
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-#pragma unroll
-        for (int step = 0; step < 2; ++step) {
-          bf16x8v dof2, qf2;
-          {
-            const int kb = step * 16 + 8 * hi;
-            const int o0 = tr16_b_off<true>(lane, kb, hh);
-            const int o1 = tr16_b_off<true>(lane, kb + 4, hh);
-            bf16x4v a0 = DS_TR16(do_lds + o0), a1 = DS_TR16(do_lds + o1);
-            bf16x4v b0 = DS_TR16(q_lds + o0), b1 = DS_TR16(q_lds + o1);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              dof2[e] = a0[e]; dof2[e + 4] = a1[e];
-              qf2[e] = b0[e]; qf2[e + 4] = b1[e];
-            }
-          }
-          dv_acc[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<const bf16x8v*>(&pa_p[step][0]), dof2,
-              dv_acc[hh], 0, 0, 0);
-          dk_acc[hh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<const bf16x8v*>(&pa_ds[step][0]), qf2,
-              dk_acc[hh], 0, 0, 0);
-        }
-      }
-    }
-  }
-  if (!live_wave) return;
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      if (krow < S) {
-        const long off = (long)krow * sg.rs + hh * 32 + j32;
-        dvp[off] = f2bf(dv_acc[hh][r]);
-        dkp[off] = f2bf(dk_acc[hh][r]);
-      }
-    }
-  }
-}
-
-// -------------------------------------------------------------------
 // dq kernel: wave owns q rows [q0, q0+32); loops kv tiles (forward
 // orientation: acc = [key-pattern][qrow=lane&31]).
 // -------------------------------------------------------------------
@@ -790,7 +591,8 @@ std::vector<at::Tensor> attn_bwd_impl(
     bool causal, double scale, long B, long H, int S, StridesB sio,
     StridesB sdo, StridesB sg, bf16_t* dqb, bf16_t* dkb, bf16_t* dvb,
     const at::TensorOptions& fopt, const int* kvl, int D,
-    float pdrop = 0.f, const unsigned* mbits = nullptr) {
+    c10::optional<bool> bwd64, float pdrop = 0.f,
+    const unsigned* mbits = nullptr) {
   const float inv_keep = 1.f / (1.f - pdrop);
   auto delta = at::empty({B * H * (long)S}, fopt);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
@@ -804,21 +606,29 @@ std::vector<at::Tensor> attn_bwd_impl(
     HIP_CHECK_LAST();
     return {};
   }
+  // 64-row stages are the measured default (profiles/attn_bwd64.txt);
+  // RAVNEST_ATTN_BWD64=0, or bwd64 = false per call, keeps the 32-row
+  // kernels below
+  static const bool bwd64_env = [] {
+    const char* e = getenv("RAVNEST_ATTN_BWD64");
+    return !(e && e[0] == '0');
+  }();
+  if (pdrop == 0.f && bwd64.value_or(bwd64_env)) {
+    attn_bwd64_launch(qb, kb, vb, ob, dob, lse.data_ptr<float>(),
+                      delta.data_ptr<float>(), mask_ptr, causal,
+                      (float)scale, B, H, S, sio, sdo, sg, dqb, dkb, dvb,
+                      kvl, stream);
+    HIP_CHECK_LAST();
+    return {};
+  }
   const long NR = B * H * (long)S;
   hipLaunchKernelGGL((attn_bwd_delta_kernel<64>),
                      dim3((NR * 8 + 255) / 256), dim3(256), 0, stream, dob,
                      ob, delta.data_ptr<float>(), S, H, NR, sdo);
   dim3 block(256);
   dim3 gridk((S + 127) / 128, B * H);
-  // split is the measured default: the merged kernel lands at 210 VGPRs
-  // (2 waves/SIMD) and runs at 161 TF vs the split pair's 270 TF
-  static const bool split_dkv = [] {
-    const char* e = getenv("RAVNEST_ATTN_MERGED_DKV");
-    return !(e && e[0] == '1');
-  }();
-  TORCH_CHECK(pdrop == 0.f || (split_dkv && mbits != nullptr),
-              "attn_bwd: fused prob-dropout needs the split dv/dk path "
-              "and the fwd's mask words");
+  TORCH_CHECK(pdrop == 0.f || mbits != nullptr,
+              "attn_bwd: fused prob-dropout needs the fwd's mask words");
   if (pdrop > 0.f) {
     hipLaunchKernelGGL((attn_bwd_dv_kernel<true>), gridk, block, 0, stream,
                        qb, kb, dob, lse.data_ptr<float>(), mask_ptr, dvb, S,
@@ -837,25 +647,17 @@ std::vector<at::Tensor> attn_bwd_impl(
     HIP_CHECK_LAST();
     return {};
   }
-  if (split_dkv) {
-    hipLaunchKernelGGL((attn_bwd_dv_kernel<false>), gridk, block, 0, stream,
-                       qb, kb,
-                       dob, lse.data_ptr<float>(), mask_ptr, dvb, S,
-                       causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg, kvl);
-    hipLaunchKernelGGL((attn_bwd_dk_kernel<false>), gridk, block, 0, stream,
-                       qb, kb,
-                       vb, dob, lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), mask_ptr, dkb, S,
-                       causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg, kvl);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dvdk_kernel, gridk, block, 0, stream, qb,
-                       kb, vb, dob, lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), mask_ptr, dkb, dvb, S,
-                       causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
-                       sio, sdo, sg, kvl);
-  }
+  hipLaunchKernelGGL((attn_bwd_dv_kernel<false>), gridk, block, 0, stream,
+                     qb, kb,
+                     dob, lse.data_ptr<float>(), mask_ptr, dvb, S,
+                     causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
+                     sio, sdo, sg, kvl);
+  hipLaunchKernelGGL((attn_bwd_dk_kernel<false>), gridk, block, 0, stream,
+                     qb, kb,
+                     vb, dob, lse.data_ptr<float>(),
+                     delta.data_ptr<float>(), mask_ptr, dkb, S,
+                     causal ? 1 : 0, (float)scale, has_mask ? 1 : 0, H,
+                     sio, sdo, sg, kvl);
   hipLaunchKernelGGL((attn_bwd_dq_kernel<false>), gridk, block, 0, stream,
                      qb, kb,
                      vb, dob, lse.data_ptr<float>(), delta.data_ptr<float>(),
@@ -871,7 +673,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor dout,
                                  at::Tensor lse, at::Tensor mask, bool causal,
                                  double scale,
-                                 c10::optional<at::Tensor> kv_len) {
+                                 c10::optional<at::Tensor> kv_len,
+                                 c10::optional<bool> bwd64) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
               v.is_contiguous() && o.is_contiguous());
   TORCH_CHECK(q.scalar_type() == at::kBFloat16);
@@ -900,7 +703,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                 reinterpret_cast<bf16_t*>(dq.data_ptr()),
                 reinterpret_cast<bf16_t*>(dk.data_ptr()),
                 reinterpret_cast<bf16_t*>(dv.data_ptr()),
-                q.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B), D);
+                q.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B), D,
+                bwd64);
   return {dq, dk, dv};
 }
 
@@ -909,7 +713,8 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         at::Tensor lse, at::Tensor mask, bool causal,
                         double scale, double pdrop,
                         c10::optional<at::Tensor> mbits,
-                        c10::optional<at::Tensor> kv_len) {
+                        c10::optional<at::Tensor> kv_len,
+                        c10::optional<bool> bwd64) {
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && o.is_contiguous());
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3);
   const long B = qkv.size(0), H = qkv.size(3);
@@ -940,6 +745,6 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                 mask_ptr, has_mask, causal, scale, B, H, S, sp, sod, sp,
                 dbase, dbase + HD, dbase + 2 * HD,
                 qkv.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B),
-                D, (float)pdrop, mb);
+                D, bwd64, (float)pdrop, mb);
   return dqkv;
 }

@@ -1,7 +1,7 @@
-// Pieces shared by the flash-attention backward kernels of both head
-// dimensions (attention_bwd.hip: D=64, attention_bwd128.hip: D=128): the
-// stride triple, the tr16 read, the MFMA C-layout -> A-fragment repack
-// and the Delta kernel.
+// Pieces shared by the flash-attention backward kernels (attention_bwd.hip
+// and attention_bwd64.hip: D=64, attention_bwd128.hip: D=128): the stride
+// triple, the tr16 read and its offsets in the D=64 LDS image, the MFMA
+// C-layout -> A-fragment repack and the Delta kernel.
 #pragma once
 
 #include "common.h"
@@ -48,6 +48,21 @@ DEVINL void acc_to_afrag(const f32x16& acc, unsigned int pa[2][4]) {
   }
 }
 
+// per-lane byte offset for a tr16 B-fragment read of
+// B[k = kbase + 0..3][j = hh*32 + (lane&31)] from a 128-B-row LDS image,
+// optionally XOR-swizzled ((row&15)<<4, 16-B granularity — an 8-B-aligned
+// read never crosses the flipped boundary). The row-dependent XOR also
+// de-conflicts the 4-lanes-per-row gather (rows r and r+2 land 32 B
+// apart), so the swizzled images need no extra padding.
+template <bool SWZ>
+DEVINL int tr16_b_off(int lane, int kbase, int hh) {
+  const int q4 = lane & 15;
+  const int row = kbase + (q4 >> 2);
+  int off = row * 128 + hh * 64 + ((lane >> 4) & 1) * 32 + 8 * (q4 & 3);
+  if (SWZ) off ^= (row & 15) << 4;
+  return off;
+}
+
 // Delta[row] = sum_d dO[row][d] * O[row][d]. D/8 lanes per row, bf16x8
 // loads (the one-wave-per-row 2-B-scalar version measured 7x off the
 // bandwidth bound at 2.5% of the BERT step — rocprofv3 r01 final).
@@ -84,3 +99,12 @@ void attn_bwd_d128_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                           StridesB sio, StridesB sdo, StridesB sg,
                           bf16_t* dq, bf16_t* dk, bf16_t* dv, const int* kvl,
                           hipStream_t stream);
+
+// D=64 backward on 64-row stages (attention_bwd64.hip): Delta, dK+dV, dQ
+// on `stream`; same contract as attn_bwd_d128_launch.
+void attn_bwd64_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v,
+                       const bf16_t* o, const bf16_t* dout, const float* lse,
+                       float* delta, const float* mask, bool causal,
+                       float scale, long B, long H, int S, StridesB sio,
+                       StridesB sdo, StridesB sg, bf16_t* dq, bf16_t* dk,
+                       bf16_t* dv, const int* kvl, hipStream_t stream);

@@ -136,7 +136,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor dout,
                                  at::Tensor lse, at::Tensor mask, bool causal,
                                  double scale,
-                                 c10::optional<at::Tensor> kv_len);
+                                 c10::optional<at::Tensor> kv_len,
+                                 c10::optional<bool> bwd64);
 std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                                      bool causal, double scale,
                                      double pdrop, int64_t dseed,
@@ -146,7 +147,8 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         at::Tensor lse, at::Tensor mask, bool causal,
                         double scale, double pdrop,
                         c10::optional<at::Tensor> mbits,
-                        c10::optional<at::Tensor> kv_len);
+                        c10::optional<at::Tensor> kv_len,
+                        c10::optional<bool> bwd64);
 at::Tensor attn_mask_kv_len(at::Tensor mask);
 at::Tensor mfma_probe(at::Tensor a, at::Tensor b);
 at::Tensor tr16_probe();
@@ -298,7 +300,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("dout"), py::arg("lse"), py::arg("mask"), py::arg("causal"),
         py::arg("scale"), py::arg("kv_len") = py::none(),
-        "flash attention bwd (bf16, MFMA, D=64)");
+        py::arg("bwd64") = py::none(),
+        "flash attention bwd (bf16, MFMA); bwd64: D=64 kernels on 64-row "
+        "stages (true) or 32-row tiles (false), none = RAVNEST_ATTN_BWD64");
   m.def("attn_fwd_qkv", &attn_fwd_qkv,
         py::arg("qkv"), py::arg("mask"), py::arg("causal"),
         py::arg("scale"), py::arg("pdrop") = 0.0, py::arg("dseed") = 0,
@@ -308,7 +312,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("lse"),
         py::arg("mask"), py::arg("causal"), py::arg("scale"),
         py::arg("pdrop") = 0.0, py::arg("mbits") = py::none(),
-        py::arg("kv_len") = py::none(),
+        py::arg("kv_len") = py::none(), py::arg("bwd64") = py::none(),
         "flash attention bwd, packed qkv -> dqkv");
   m.def("attn_mask_kv_len", &attn_mask_kv_len, py::arg("mask"),
         "additive (B,S) padding mask -> int32[B] key horizon");

@@ -6,9 +6,14 @@ SURVEY.md section 2.3. Forward is the hand-written HIP kernel
 (csrc/attention.hip): per Q-tile online-softmax over K/V tiles, bf16 MFMA
 (32x32x16), XOR-swizzled K LDS tiles, no S x S score matrix in HBM; it
 returns O and the log-sum-exp rows. Backward runs the fused flash
-backward kernels (delta + dv + dk + dq, P recomputed from (Q,K,lse)
-on-chip): csrc/attention_bwd.hip at D=64, csrc/attention_bwd128.hip at
-D=128, separate and packed layouts alike. BWD_D128 off
+backward kernels (P recomputed from (Q,K,lse) on-chip), separate and
+packed layouts alike. At D=64 that is csrc/attention_bwd64.hip: delta,
+one kernel for dK and dV, one for dQ, both on 64-row stages (7 matmul
+passes, 3 launches). BWD64 off (RAVNEST_ATTN_BWD64=0) keeps the earlier
+delta + dv + dk + dq kernels on 32-row tiles of csrc/attention_bwd.hip
+(8 passes, 4 launches), which fused probability dropout always uses; it
+is the A/B arm of tools/attn_bench.py. At D=128 it is
+csrc/attention_bwd128.hip (delta + dv + dk + dq). BWD_D128 off
 (RAVNEST_ATTN_BWD_D128=0) sends D=128 back to the composed backward that
 recomputes P with hipBLASLt GEMMs + elementwise torch and materialises
 (B,H,S,S) tensors; it is kept as the A/B arm of tools/attn_bench.py.
@@ -47,6 +52,10 @@ KV_SKIP = os.environ.get("RAVNEST_ATTN_KV_SKIP", "0") == "1"
 # D=128 backward through the flash kernels (and the packed layout through
 # _AttnQKVFn). Read at call time; off = the composed backward.
 BWD_D128 = os.environ.get("RAVNEST_ATTN_BWD_D128", "1") != "0"
+
+# D=64 backward on 64-row stages with the merged dK/dV kernel. Read at
+# call time; off = the 32-row dv, dk and dq kernels.
+BWD64 = os.environ.get("RAVNEST_ATTN_BWD64", "1") != "0"
 
 
 def kv_len_from_mask(mask):
@@ -125,7 +134,7 @@ class _AttnFn(torch.autograd.Function):
             dq, dk, dv = ext.attn_bwd(
                 q, k, v, o, do, lse,
                 mask if mask is not None else torch.Tensor(), causal, scale,
-                kv_len)
+                kv_len, BWD64)
             return dq, dk, dv, None, None, None, None
         # composed arm (D=128 with BWD_D128 off): recompute P from lse via
         # library GEMMs
@@ -218,7 +227,7 @@ class _AttnQKVFn(torch.autograd.Function):
         dqkv = ext.attn_bwd_qkv(
             qkv, o, do.contiguous(), lse,
             mask if mask is not None else torch.Tensor(),
-            ctx.causal, ctx.scale, ctx.pdrop, mbits, kv_len)
+            ctx.causal, ctx.scale, ctx.pdrop, mbits, kv_len, BWD64)
         return dqkv, None, None, None, None, None
 
 

@@ -17,6 +17,13 @@ round in one process: the flash kernels (BWD_D128 on; separate and packed
 layouts) and the composed torch backward (BWD_D128 off, what
 RAVNEST_ATTN_BWD_D128=0 selects). --causal for the causal case. Medians
 with min..max; TF/s over the 7 matmul passes (halved work when causal).
+
+--D 64 (default): fwd once, then the backward on both arms, alternated
+round after round in one process: the 64-row-stage kernels (bwd64: Delta,
+dK+dV, dQ = 7 executed matmul passes) and the 32-row kernels (rows32:
+Delta, dV, dK, dQ = 8 executed passes), separate and packed layouts.
+Medians with min..max; TF/s on the executed passes and on the 5 passes
+the result needs (halved work when causal).
 """
 import argparse
 import math
@@ -174,29 +181,51 @@ def main():
                    args.iters)
         return
 
-    # FLOPs: fwd 2 matmuls, bwd 7 matmul passes (S,dP twice + dV,dK,dQ)
-    mm = 2 * B * H * S * S * D  # one S x S x D matmul pass (x2 flops)
-    fwd_fl, bwd_fl = 2 * mm, 7 * mm
+    bench_d64(ext, dev, B, S, H, D, args.causal, args.rounds, args.iters)
 
+
+def bench_d64(ext, dev, B, S, H, D, causal, rounds, iters):
+    scale = 1.0 / math.sqrt(D)
+    empty = torch.Tensor()
+    mm = 2 * B * H * S * S * D * (0.5 if causal else 1.0)  # one matmul pass
     q, k, v = (torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16)
                for _ in range(3))
-    empty = torch.Tensor()
-    o, lse = ext.attn_fwd(q, k, v, empty, False, scale)
+    o, lse = ext.attn_fwd(q, k, v, empty, causal, scale)
     do = torch.randn_like(o)
-    t_f = timeit(lambda: ext.attn_fwd(q, k, v, empty, False, scale))
-    t_b = timeit(lambda: ext.attn_bwd(q, k, v, o, do, lse, empty, False,
-                                      scale))
-    print(f"separate: fwd {t_f:7.3f} ms ({fwd_fl/t_f/1e9:7.1f} TF/s)  "
-          f"bwd {t_b:7.3f} ms ({bwd_fl/t_b/1e9:7.1f} TF/s)")
-
     qkv = torch.randn(B, S, 3, H, D, device=dev, dtype=torch.bfloat16)
-    o2, lse2 = ext.attn_fwd_qkv(qkv, empty, False, scale)
+    o2, lse2 = ext.attn_fwd_qkv(qkv, empty, causal, scale)[:2]
     do2 = torch.randn_like(o2)
-    t_f2 = timeit(lambda: ext.attn_fwd_qkv(qkv, empty, False, scale))
-    t_b2 = timeit(lambda: ext.attn_bwd_qkv(qkv, o2, do2, lse2, empty, False,
-                                           scale))
-    print(f"packed:   fwd {t_f2:7.3f} ms ({fwd_fl/t_f2/1e9:7.1f} TF/s)  "
-          f"bwd {t_b2:7.3f} ms ({bwd_fl/t_b2/1e9:7.1f} TF/s)")
+    t_f = timeit(lambda: ext.attn_fwd(q, k, v, empty, causal, scale), iters)
+    t_f2 = timeit(lambda: ext.attn_fwd_qkv(qkv, empty, causal, scale), iters)
+
+    def sep(flag):
+        return lambda: ext.attn_bwd(q, k, v, o, do, lse, empty, causal,
+                                    scale, None, flag)
+
+    def packed(flag):
+        return lambda: ext.attn_bwd_qkv(qkv, o2, do2, lse2, empty, causal,
+                                        scale, 0.0, None, None, flag)
+
+    # arm -> (callable, executed matmul passes)
+    arms = {"rows32 separate": (sep(False), 8),
+            "bwd64 separate": (sep(True), 7),
+            "rows32 packed": (packed(False), 8),
+            "bwd64 packed": (packed(True), 7)}
+    t = {a: [] for a in arms}
+    for _ in range(rounds):
+        for a, (fn, _) in arms.items():
+            t[a].append(timeit(fn, iters, 2))
+    print(f"B={B} H={H} S={S} D={D} causal={causal}: fwd separate "
+          f"{t_f:7.3f} ms ({2 * mm / t_f / 1e9:6.1f} TF/s), packed "
+          f"{t_f2:7.3f} ms ({2 * mm / t_f2 / 1e9:6.1f} TF/s); bwd {rounds} "
+          f"rounds x {iters} iters per arm, arms alternated; ms median "
+          f"[min..max]")
+    for a, (_, passes) in arms.items():
+        x = t[a]
+        med = statistics.median(x)
+        print(f"  bwd {a:16s} {med:8.3f} [{min(x):8.3f}..{max(x):8.3f}] "
+              f"({passes * mm / med / 1e9:6.1f} TF/s executed, "
+              f"{5 * mm / med / 1e9:6.1f} useful)")
 
 
 if __name__ == "__main__":
