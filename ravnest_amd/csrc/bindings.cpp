@@ -150,6 +150,11 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         c10::optional<at::Tensor> kv_len,
                         c10::optional<bool> bwd64);
 at::Tensor attn_mask_kv_len(at::Tensor mask);
+at::Tensor attn_decode(at::Tensor qkv_new, at::Tensor k_cache,
+                       at::Tensor v_cache, at::Tensor cache_len, double scale,
+                       c10::optional<int64_t> max_len,
+                       c10::optional<int64_t> n_split);
+int64_t attn_decode_splits(int64_t bh, int64_t max_len);
 at::Tensor mfma_probe(at::Tensor a, at::Tensor b);
 at::Tensor tr16_probe();
 at::Tensor mfma_mx_probe(at::Tensor a, at::Tensor b, int64_t sa, int64_t sb);
@@ -316,6 +321,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash attention bwd, packed qkv -> dqkv");
   m.def("attn_mask_kv_len", &attn_mask_kv_len, py::arg("mask"),
         "additive (B,S) padding mask -> int32[B] key horizon");
+  m.def("attn_decode", &attn_decode,
+        py::arg("qkv_new"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("cache_len"), py::arg("scale"),
+        py::arg("max_len") = py::none(), py::arg("n_split") = py::none(),
+        "split-KV decode attention: qkv_new (B,3,H,D) against (B,H,S_max,D) "
+        "caches, appends row cache_len[b] in place -> o (B,H*D)");
+  m.def("attn_decode_splits", &attn_decode_splits, py::arg("bh"),
+        py::arg("max_len"),
+        "split count attn_decode picks for B*H heads and max_len keys");
   m.def("mfma_probe", &mfma_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 mapping probe");
   m.def("mfma_mx_probe", &mfma_mx_probe,

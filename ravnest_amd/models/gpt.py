@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from ..ops import (AttentionCoreQKV, Dropout, FusedLayerNorm,
                    LinearGelu, MXLinear)
-from ..ops import embedding_add
+from ..ops import attention_decode, embedding_add
 
 
 class GPTConfig:
@@ -108,6 +108,32 @@ class GPTBlock(nn.Module):
         x = x + self.mlp_drop(self.mlp_out(self.mlp_in(self.ln2(x))))
         return x
 
+    def prefill(self, x, cache):
+        """forward() over the prompt (B,S,C) that also copies the prompt's
+        keys and values into rows [0, S) of cache = (k_cache, v_cache),
+        each (B, H, block_size, D)."""
+        h = self.ln1(x)
+        qkv = self.qkv(h).unflatten(-1, (3, self.n_head, self.head_dim))
+        S = x.size(1)
+        cache[0][:, :, :S].copy_(qkv[:, :, 1].transpose(1, 2))
+        cache[1][:, :, :S].copy_(qkv[:, :, 2].transpose(1, 2))
+        o = self.core(qkv)
+        x = x + self.attn_drop(self.proj(o))
+        x = x + self.mlp_drop(self.mlp_out(self.mlp_in(self.ln2(x))))
+        return x
+
+    def decode(self, x, cache, cache_len, max_len=None):
+        """One cached step: x (B,1,C) is the new token, cache_len (B,)
+        int32 the keys already cached. Appends the token's k and v to the
+        caches in place; the caller advances cache_len."""
+        B = x.size(0)
+        qkv = self.qkv(self.ln1(x)).view(B, 3, self.n_head, self.head_dim)
+        o = attention_decode(qkv, cache[0], cache[1], cache_len,
+                             max_len=max_len)
+        x = x + self.attn_drop(self.proj(o.unsqueeze(1)))
+        x = x + self.mlp_drop(self.mlp_out(self.mlp_in(self.ln2(x))))
+        return x
+
 
 class GPT(nn.Module):
     """idx (B,S) int64 -> logits (B,S,V)."""
@@ -140,13 +166,59 @@ class GPT(nn.Module):
         return self.lm_head(self.ln_f(x))
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens):
+    def generate(self, idx, max_new_tokens, use_cache=False):
         """Greedy decode (parity: sorter inference,
-        examples/sorter/mingpt/utils.py)."""
+        examples/sorter/mingpt/utils.py).
+
+        use_cache=True keeps a key/value cache per block: one causal
+        forward over the prompt, then one-token steps on the decode
+        attention kernel instead of a full forward per token. Absolute
+        position embeddings cannot slide a cached window, so the prompt
+        plus max_new_tokens must fit block_size; fp8 models are not
+        supported."""
         self.eval()
+        if use_cache:
+            return self._generate_cached(idx, max_new_tokens)
         for _ in range(max_new_tokens):
             idx_cond = idx[:, -self.cfg.block_size:]
             logits = self(idx_cond)
             nxt = logits[:, -1, :].argmax(dim=-1, keepdim=True)
             idx = torch.cat([idx, nxt], dim=1)
+        return idx
+
+    def _generate_cached(self, idx, max_new_tokens):
+        cfg = self.cfg
+        B, S0 = idx.shape
+        if S0 + max_new_tokens > cfg.block_size:
+            raise ValueError(
+                f"use_cache=True needs prompt ({S0}) + max_new_tokens "
+                f"({max_new_tokens}) <= block_size ({cfg.block_size})")
+        if getattr(cfg, "fp8", False):
+            raise ValueError("use_cache=True does not support fp8 models")
+        if max_new_tokens <= 0:
+            return idx
+        emb = self.embeddings
+        w = emb.tok_emb.weight
+        shape = (B, cfg.n_head, cfg.block_size, cfg.n_embd // cfg.n_head)
+        caches = [(torch.zeros(shape, dtype=w.dtype, device=w.device),
+                   torch.zeros(shape, dtype=w.dtype, device=w.device))
+                  for _ in self.blocks]
+        # one counter for all layers, read by the kernels on the device
+        cache_len = torch.full((B,), S0, dtype=torch.int32, device=w.device)
+        x = emb(idx)
+        for blk, cache in zip(self.blocks, caches):
+            x = blk.prefill(x, cache)
+        logits = self.lm_head(self.ln_f(x[:, -1:]))
+        nxt = logits[:, -1, :].argmax(dim=-1, keepdim=True)
+        idx = torch.cat([idx, nxt], dim=1)
+        for step in range(1, max_new_tokens):
+            x = emb.tok_emb(nxt) + emb.pos_emb(cache_len.long())[:, None]
+            x = emb.drop(x)
+            for blk, cache in zip(self.blocks, caches):
+                # this step's token sits at row S0 + step - 1
+                x = blk.decode(x, cache, cache_len, max_len=S0 + step)
+            logits = self.lm_head(self.ln_f(x))
+            nxt = logits[:, -1, :].argmax(dim=-1, keepdim=True)
+            idx = torch.cat([idx, nxt], dim=1)
+            cache_len += 1
         return idx

@@ -17,6 +17,9 @@ csrc/attention_bwd128.hip (delta + dv + dk + dq). BWD_D128 off
 (RAVNEST_ATTN_BWD_D128=0) sends D=128 back to the composed backward that
 recomputes P with hipBLASLt GEMMs + elementwise torch and materialises
 (B,H,S,S) tensors; it is kept as the A/B arm of tools/attn_bench.py.
+Cached decoding, one new query per head against a key/value cache, is
+csrc/attention_decode.hip (attention_decode below): split-KV, fp32
+vector math, no MFMA, no backward.
 
 Shapes: q,k,v (B, H, S, D); additive mask broadcastable to (B, 1, S, S)
 or None; causal flag for GPT-style models.
@@ -320,3 +323,71 @@ class AttentionCoreQKV(nn.Module):
                 self.training, kv_len)
         return attention_qkv(qkv, mask=mask, causal=self.causal,
                              kv_len=kv_len)
+
+
+def _decode_twin(qkv_new, k_cache, v_cache, cache_len, scale):
+    """Composed torch form of csrc/attention_decode.hip, same semantics:
+    row L = cache_len[b] of the caches takes the new token's k and v in
+    place (nothing is stored for L outside [0, S_max)), the query attends
+    rows [0, L], softmax in fp32. Rows past L never reach the result,
+    whatever they hold."""
+    S_max = k_cache.shape[2]
+    q, k, v = qkv_new.unbind(1)                       # (B, H, D) each
+    L = cache_len.long()
+    ok = ((L >= 0) & (L < S_max))[:, None, None, None]
+    Lc = L.clamp(0, S_max - 1)
+    idx = Lc[:, None, None, None].expand(-1, k.shape[1], 1, k.shape[2])
+    for cache, new in ((k_cache, k), (v_cache, v)):
+        row = torch.where(ok, new[:, :, None, :], cache.gather(2, idx))
+        cache.scatter_(2, idx, row)
+    dead = torch.arange(S_max, device=L.device)[None, :] > Lc[:, None]
+    dead = dead[:, None, :, None]                     # (B, 1, S_max, 1)
+    kf = k_cache.float().masked_fill(dead, 0.0)
+    vf = v_cache.float().masked_fill(dead, 0.0)
+    s = (kf @ q.float()[..., None]) * scale           # (B, H, S_max, 1)
+    p = torch.softmax(s.masked_fill(dead, float("-inf")), dim=2)
+    o = (p * vf).sum(dim=2)                           # (B, H, D)
+    return o.flatten(1).to(qkv_new.dtype)
+
+
+def attention_decode(qkv_new, k_cache, v_cache, cache_len, scale=None,
+                     max_len=None, n_split=None):
+    """One cached decoding step for every head of a batch.
+
+    qkv_new (B,3,H,D): the qkv projection of the one new token.
+    k_cache, v_cache (B,H,S_max,D): contiguous, updated in place.
+    cache_len (B,) int32 on the device of the caches: keys already cached
+    per sequence; read on the device only, never changed here (the caller
+    adds 1 once per step for all layers).
+    Sequence b with L = cache_len[b]: the new k and v go to row L, the
+    query attends rows [0, L]. L >= S_max stores nothing and leaves that
+    output row unspecified. Returns o (B, H*D), the layout proj reads.
+
+    max_len: host-side upper bound on L + 1 (None = S_max); n_split: split
+    count, None = chosen from B*H and max_len. Both only steer how the
+    kernel divides the keys. CUDA + bf16 + D in (64, 128) runs
+    csrc/attention_decode.hip; everything else the composed twin.
+    Inference only: raises if an input requires grad."""
+    if any(t.requires_grad for t in (qkv_new, k_cache, v_cache)):
+        raise RuntimeError("attention_decode is inference-only: run it "
+                           "under torch.no_grad() on detached tensors")
+    if qkv_new.dim() != 4 or qkv_new.shape[1] != 3:
+        raise ValueError("qkv_new must be (B, 3, H, D)")
+    B, _, H, D = qkv_new.shape
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 \
+            or k_cache.shape[0] != B or k_cache.shape[1] != H \
+            or k_cache.shape[3] != D:
+        raise ValueError("k_cache and v_cache must be (B, H, S_max, D)")
+    if cache_len.shape != (B,) or cache_len.dtype != torch.int32 \
+            or cache_len.device != k_cache.device:
+        raise ValueError(f"cache_len must be int32 of shape ({B},) on the "
+                         "caches' device")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if qkv_new.is_cuda and qkv_new.dtype == torch.bfloat16 \
+            and k_cache.dtype == torch.bfloat16 and D in (64, 128):
+        ext = get_ext(required=True)
+        return ext.attn_decode(qkv_new.contiguous(), k_cache, v_cache,
+                               cache_len, scale, max_len, n_split)
+    with torch.no_grad():
+        return _decode_twin(qkv_new, k_cache, v_cache, cache_len, scale)

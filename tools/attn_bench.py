@@ -24,6 +24,16 @@ dK+dV, dQ = 7 executed matmul passes) and the 32-row kernels (rows32:
 Delta, dV, dK, dQ = 8 executed passes), separate and packed layouts.
 Medians with min..max; TF/s on the executed passes and on the 5 passes
 the result needs (halved work when causal).
+
+--decode: cached decoding. Kernel alone: attention_decode against its
+composed torch twin, alternated round after round, at B = 8, 32 x
+(H=12, D=64), (H=16, D=128) x L = 128, 512, 1023 cached keys inside
+S_max = 1024, max_len = L + 1 as generate passes it; time per call
+(host enqueue included, which is what the small shapes measure), the
+chosen n_split and achieved bytes/s over the live cache (2*B*H*(L+1)*D*2
+bytes) next to the HBM peak. End to end (--decode-e2e): gpt2_small in
+bf16, B = 8, prompt 128, 128 new tokens, then B = 32, prompt 512;
+tokens/s of generate(use_cache=True) against use_cache=False, alternated.
 """
 import argparse
 import math
@@ -155,6 +165,75 @@ def bench_d128(ext, dev, B, S, H, D, causal, rounds, iters):
               f"({7 * mm / med / 1e9:6.1f} TF/s)")
 
 
+HBM_PEAK = 8.0e12  # bytes/s, MI355X HBM3E
+
+
+def bench_decode(ext, dev, rounds, iters):
+    from ravnest_amd.ops.attention import _decode_twin, attention_decode
+    S_max = 1024
+    print(f"attention_decode, S_max={S_max}, max_len=L+1; {rounds} rounds x "
+          f"{iters} iters per arm, arms alternated; us median [min..max]; "
+          f"GB/s over the live cache, HBM peak {HBM_PEAK / 1e9:.0f} GB/s")
+    for H, D in ((12, 64), (16, 128)):
+        scale = 1.0 / math.sqrt(D)
+        for B in (8, 32):
+            qkv = torch.randn(B, 3, H, D, device=dev, dtype=torch.bfloat16)
+            kc = torch.randn(B, H, S_max, D, device=dev,
+                             dtype=torch.bfloat16)
+            vc = torch.randn_like(kc)
+            for L in (128, 512, 1023):
+                cl = torch.full((B,), L, dtype=torch.int32, device=dev)
+                arms = {
+                    "kernel": lambda: attention_decode(qkv, kc, vc, cl,
+                                                       max_len=L + 1),
+                    "twin": lambda: _decode_twin(qkv, kc, vc, cl, scale),
+                }
+                t = {a: [] for a in arms}
+                for _ in range(rounds):
+                    for a, fn in arms.items():
+                        t[a].append(timeit(fn, iters, 3) * 1e3)
+                nbytes = 2 * B * H * (L + 1) * D * 2
+                ns = ext.attn_decode_splits(B * H, L + 1)
+                line = f"B={B:2d} H={H} D={D:3d} L={L:4d} n_split={ns:2d}:"
+                for a, x in t.items():
+                    med = statistics.median(x)
+                    line += (f"  {a} {med:8.1f} [{min(x):8.1f}..{max(x):8.1f}]"
+                             f" {nbytes / med / 1e3:7.1f} GB/s")
+                print(line)
+
+
+def bench_decode_e2e(dev, rounds):
+    import time
+    from ravnest_amd.models.gpt import GPT, GPTConfig
+    torch.manual_seed(0)
+    cfg = GPTConfig.gpt2_small()
+    model = GPT(cfg).to(dev).to(torch.bfloat16).eval()
+    # the issue's shape, then one with enough work per step to leave the
+    # launch-bound regime
+    for B, S0, new in ((8, 128, 128), (32, 512, 128)):
+        idx = torch.randint(0, cfg.vocab_size, (B, S0), device=dev)
+
+        def run(use_cache):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            model.generate(idx, new, use_cache=use_cache)
+            torch.cuda.synchronize()
+            return B * new / (time.perf_counter() - t0)
+
+        t = {True: [], False: []}
+        for flag in t:
+            run(flag)  # warm-up: every shape of the timed window
+        for _ in range(rounds):
+            for flag in t:
+                t[flag].append(run(flag))
+        print(f"gpt2_small bf16 generate, B={B} prompt={S0} new={new}; "
+              f"{rounds} rounds, arms alternated; tokens/s median "
+              f"[min..max]")
+        for flag, x in t.items():
+            print(f"  use_cache={flag!s:5s} {statistics.median(x):9.1f} "
+                  f"[{min(x):9.1f}..{max(x):9.1f}]")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
@@ -164,6 +243,10 @@ def main():
     ap.add_argument("--fill", type=float, nargs="+", default=None,
                     help="live share(s) of a right-padded batch")
     ap.add_argument("--causal", action="store_true")
+    ap.add_argument("--decode", action="store_true",
+                    help="decode attention kernel against its torch twin")
+    ap.add_argument("--decode-e2e", action="store_true",
+                    help="gpt2_small generate, cached against uncached")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50)
     args = ap.parse_args()
@@ -173,6 +256,12 @@ def main():
     B, S, H, D = args.B, args.S, args.H, args.D
     scale = 1.0 / math.sqrt(D)
     torch.manual_seed(0)
+    if args.decode or args.decode_e2e:
+        if args.decode:
+            bench_decode(ext, dev, args.rounds, args.iters)
+        if args.decode_e2e:
+            bench_decode_e2e(dev, min(args.rounds, 5))
+        return
     if args.fill:
         bench_fill(ext, dev, B, S, H, D, args.fill, args.rounds, args.iters)
         return
