@@ -21,21 +21,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "attention_bwd_common.h"
 #include "attention_kv_len.h"
-#include "common.h"
-
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// hardware transpose read (guide T10; exact semantics verified on-device
-// by tr16_probe): every lane supplies its OWN 8-B-aligned address and
-// loads 4 contiguous bf16; per 16-lane group those 16 loads (in lane
-// order) form a [4][16] row-major block M, and lane q of the group
-// receives column q, i.e. M[0..3][q].
-#define DS_TR16(p) __builtin_amdgcn_ds_read_tr16_b64_v4bf16( \
-    (__attribute__((address_space(3))) bf16x4v*)( \
-        (__attribute__((address_space(3))) void*)(p)))
 
 namespace {
 
@@ -600,6 +587,19 @@ static const bool use_tr16 = [] {
   return !(e && e[0] == '0');  // default: hardware-transpose V reads
 }();
 
+// 64-key stages are the measured default at D=64 without probability
+// dropout (profiles/attn_fwd64.txt); RAVNEST_ATTN_FWD64=0, or
+// fwd64 = false per call, keeps attn_fwd_lds_kernel
+static bool use_fwd64(const c10::optional<bool>& fwd64, int D) {
+  static const bool env = [] {
+    const char* e = getenv("RAVNEST_ATTN_FWD64");
+    return !(e && e[0] == '0');
+  }();
+  return D == 64 && use_lds_fwd && use_tr16 && fwd64.value_or(env);
+}
+
+static StridesB as_b(const Strides& s) { return {s.bs, s.hs, s.rs}; }
+
 // optional per-sequence key counts -> device pointer (nullptr = none)
 const int* attn_kv_len_ptr(const c10::optional<at::Tensor>& kv_len, long B) {
   if (!kv_len.has_value()) return nullptr;
@@ -628,7 +628,8 @@ at::Tensor attn_mask_kv_len(at::Tensor mask) {
 
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor mask, bool causal, double scale,
-                                 c10::optional<at::Tensor> kv_len) {
+                                 c10::optional<at::Tensor> kv_len,
+                                 c10::optional<bool> fwd64) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
               v.is_contiguous());
   TORCH_CHECK(q.dim() == 4, "q must be (B,H,S,D)");
@@ -677,7 +678,14 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                          (long)H, SQ, SK, SV, SO, kvl);                          \
   } while (0)
 
-  if (D == 64) {
+  if (use_fwd64(fwd64, D)) {
+    attn_fwd64_launch(reinterpret_cast<const bf16_t*>(q.data_ptr()),
+                      reinterpret_cast<const bf16_t*>(k.data_ptr()),
+                      reinterpret_cast<const bf16_t*>(v.data_ptr()), mask_ptr,
+                      reinterpret_cast<bf16_t*>(o.data_ptr()),
+                      lse.data_ptr<float>(), causal, (float)scale, B, H, S,
+                      as_b(sep), as_b(sep), as_b(sep), as_b(so), kvl, stream);
+  } else if (D == 64) {
     LAUNCH_ATTN_FWD(64, reinterpret_cast<const bf16_t*>(q.data_ptr()),
                     reinterpret_cast<const bf16_t*>(k.data_ptr()),
                     reinterpret_cast<const bf16_t*>(v.data_ptr()),
@@ -700,7 +708,8 @@ std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                                      bool causal, double scale,
                                      double pdrop, int64_t dseed,
                                      c10::optional<at::Tensor> seed_buf,
-                                     c10::optional<at::Tensor> kv_len) {
+                                     c10::optional<at::Tensor> kv_len,
+                                     c10::optional<bool> fwd64) {
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous());
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3,
               "qkv must be (B,S,3,H,D)");
@@ -748,6 +757,11 @@ std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                        reinterpret_cast<unsigned*>(mbits.data_ptr<int>()));
     HIP_CHECK_LAST();
     return {o, lse, mbits};
+  } else if (use_fwd64(fwd64, D)) {
+    attn_fwd64_launch(base, base + HD, base + 2 * HD, mask_ptr,
+                      reinterpret_cast<bf16_t*>(o.data_ptr()),
+                      lse.data_ptr<float>(), causal, (float)scale, B, H, S,
+                      as_b(sp), as_b(sp), as_b(sp), as_b(so), kvl, stream);
   } else if (D == 64) {
     LAUNCH_ATTN_FWD(64, base, base + HD, base + 2 * HD,
                     reinterpret_cast<bf16_t*>(o.data_ptr()), sp, sp, sp, so);

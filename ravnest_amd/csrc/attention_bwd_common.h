@@ -1,6 +1,6 @@
 // Pieces shared by the flash-attention backward kernels (attention_bwd.hip
-// and attention_bwd64.hip: D=64, attention_bwd128.hip: D=128): the stride
-// triple, the tr16 read and its offsets in the D=64 LDS image, the MFMA
+// and attention_bwd64.hip: D=64, attention_bwd128.hip: D=128) and the
+// 64-key-stage forward (attention_fwd64.hip): the stride triple, the tr16 read and its offsets in the D=64 LDS image, the MFMA
 // C-layout -> A-fragment repack and the Delta kernel.
 #pragma once
 
@@ -25,16 +25,35 @@ DEVINL unsigned int pack_bf2b(float lo, float hi) {
   return (unsigned int)f2us(lo) | ((unsigned int)f2us(hi) << 16);
 }
 
+// the same pair through the hardware conversion (v_cvt_pk_bf16_f32):
+// round-to-nearest-even as above, one instruction instead of nine
+DEVINL unsigned int pack_bf2_cvt(float lo, float hi) {
+  typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+  typedef float f32x2v __attribute__((ext_vector_type(2)));
+  const f32x2v f = {lo, hi};
+  return __builtin_bit_cast(unsigned int,
+                            __builtin_convertvector(f, bf16x2v));
+}
+
 // transform a [row-pattern][col=lane] f32 acc (16 regs) into the A-operand
 // fragments covering k=rows: pa[step] holds rows 16*step + (lane>>5)*8+e.
+// CVT: pack with pack_bf2_cvt (the forward; NaN-free inputs give the same
+// bits either way).
+template <bool CVT>
+DEVINL unsigned int pack_bf2_sel(float lo, float hi) {
+  if constexpr (CVT) return pack_bf2_cvt(lo, hi);
+  else return pack_bf2b(lo, hi);
+}
+
+template <bool CVT = false>
 DEVINL void acc_to_afrag(const f32x16& acc, unsigned int pa[2][4]) {
 #pragma unroll
   for (int step = 0; step < 2; ++step) {
     const int b0 = step * 8;
-    unsigned int c01 = pack_bf2b(acc[b0 + 0], acc[b0 + 1]);
-    unsigned int c23 = pack_bf2b(acc[b0 + 2], acc[b0 + 3]);
-    unsigned int c45 = pack_bf2b(acc[b0 + 4], acc[b0 + 5]);
-    unsigned int c67 = pack_bf2b(acc[b0 + 6], acc[b0 + 7]);
+    unsigned int c01 = pack_bf2_sel<CVT>(acc[b0 + 0], acc[b0 + 1]);
+    unsigned int c23 = pack_bf2_sel<CVT>(acc[b0 + 2], acc[b0 + 3]);
+    unsigned int c45 = pack_bf2_sel<CVT>(acc[b0 + 4], acc[b0 + 5]);
+    unsigned int c67 = pack_bf2_sel<CVT>(acc[b0 + 6], acc[b0 + 7]);
     {
       auto r2 = __builtin_amdgcn_permlane32_swap(c01, c45, false, false);
       pa[step][0] = r2[0];
@@ -108,3 +127,12 @@ void attn_bwd64_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                        float scale, long B, long H, int S, StridesB sio,
                        StridesB sdo, StridesB sg, bf16_t* dq, bf16_t* dk,
                        bf16_t* dv, const int* kvl, hipStream_t stream);
+
+// D=64 forward on 64-key stages (attention_fwd64.hip), no probability
+// dropout: o (bf16) and lse = m + ln l (fp32, B*H*S) on `stream`; mask
+// (fp32, B*S) and kvl may be null.
+void attn_fwd64_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v,
+                       const float* mask, bf16_t* o, float* lse, bool causal,
+                       float scale, long B, long H, int S, StridesB sq,
+                       StridesB sk, StridesB sv, StridesB so, const int* kvl,
+                       hipStream_t stream);

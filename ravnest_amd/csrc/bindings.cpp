@@ -131,7 +131,8 @@ void fused_lamb_table(at::Tensor table, long nchunks, long esize,
 void fused_copy(std::vector<at::Tensor> srcs, std::vector<at::Tensor> dsts);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor mask, bool causal, double scale,
-                                 c10::optional<at::Tensor> kv_len);
+                                 c10::optional<at::Tensor> kv_len,
+                                 c10::optional<bool> fwd64);
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor o, at::Tensor dout,
                                  at::Tensor lse, at::Tensor mask, bool causal,
@@ -142,7 +143,8 @@ std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                                      bool causal, double scale,
                                      double pdrop, int64_t dseed,
                                      c10::optional<at::Tensor> seed_buf,
-                                     c10::optional<at::Tensor> kv_len);
+                                     c10::optional<at::Tensor> kv_len,
+                                     c10::optional<bool> fwd64);
 at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         at::Tensor lse, at::Tensor mask, bool causal,
                         double scale, double pdrop,
@@ -300,7 +302,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd,
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("mask"),
         py::arg("causal"), py::arg("scale"), py::arg("kv_len") = py::none(),
-        "flash attention fwd (bf16, MFMA)");
+        py::arg("fwd64") = py::none(),
+        "flash attention fwd (bf16, MFMA); fwd64: D=64 kernel on 64-key "
+        "stages (true) or 32-key tiles (false), none = RAVNEST_ATTN_FWD64");
   m.def("attn_bwd", &attn_bwd,
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("dout"), py::arg("lse"), py::arg("mask"), py::arg("causal"),
@@ -312,6 +316,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("mask"), py::arg("causal"),
         py::arg("scale"), py::arg("pdrop") = 0.0, py::arg("dseed") = 0,
         py::arg("seed_buf") = py::none(), py::arg("kv_len") = py::none(),
+        py::arg("fwd64") = py::none(),
         "flash attention fwd, packed (B,S,3,H,D) qkv -> (B,S,H,D)");
   m.def("attn_bwd_qkv", &attn_bwd_qkv,
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("lse"),

@@ -2,10 +2,14 @@
 
 Reference workload parity: minGPT causal self-attention
 (model_without_padding_mask.py:50-113) and BERT's padded-mask attention —
-SURVEY.md section 2.3. Forward is the hand-written HIP kernel
-(csrc/attention.hip): per Q-tile online-softmax over K/V tiles, bf16 MFMA
-(32x32x16), XOR-swizzled K LDS tiles, no S x S score matrix in HBM; it
-returns O and the log-sum-exp rows. Backward runs the fused flash
+SURVEY.md section 2.3. Forward is the hand-written HIP kernel: per Q-tile
+online-softmax over K/V tiles, bf16 MFMA (32x32x16), XOR-swizzled LDS
+tiles, no S x S score matrix in HBM; it returns O and the log-sum-exp
+rows. At D=64 without probability dropout that is csrc/attention_fwd64.hip
+(64-key stages, K and V both staged by LDS-DMA, one running-max decision
+per stage). FWD64 off (RAVNEST_ATTN_FWD64=0) keeps the 32-key-tile kernel
+of csrc/attention.hip, which probability dropout and D=128 always use; it
+is the A/B arm of tools/attn_bench.py. Backward runs the fused flash
 backward kernels (P recomputed from (Q,K,lse) on-chip), separate and
 packed layouts alike. At D=64 that is csrc/attention_bwd64.hip: delta,
 one kernel for dK and dV, one for dQ, both on 64-row stages (7 matmul
@@ -59,6 +63,10 @@ BWD_D128 = os.environ.get("RAVNEST_ATTN_BWD_D128", "1") != "0"
 # D=64 backward on 64-row stages with the merged dK/dV kernel. Read at
 # call time; off = the 32-row dv, dk and dq kernels.
 BWD64 = os.environ.get("RAVNEST_ATTN_BWD64", "1") != "0"
+
+# D=64 forward on 64-key stages (no probability dropout). Read at call
+# time; off = the 32-key-tile kernel.
+FWD64 = os.environ.get("RAVNEST_ATTN_FWD64", "1") != "0"
 
 
 def kv_len_from_mask(mask):
@@ -119,7 +127,7 @@ class _AttnFn(torch.autograd.Function):
             kv_len = ext.attn_mask_kv_len(mask)
         o, lse = ext.attn_fwd(q, k, v,
                               mask if mask is not None else torch.Tensor(),
-                              causal, scale, kv_len)
+                              causal, scale, kv_len, FWD64)
         ctx.save_for_backward(q, k, v, mask if mask is not None else None,
                               o, lse, kv_len)
         ctx.causal = causal
@@ -213,7 +221,8 @@ class _AttnQKVFn(torch.autograd.Function):
             seed_buf = rng.device_seed_counter(qkv.device)
         res = ext.attn_fwd_qkv(qkv,
                                mask if mask is not None else torch.Tensor(),
-                               causal, scale, pdrop, seed, seed_buf, kv_len)
+                               causal, scale, pdrop, seed, seed_buf, kv_len,
+                               FWD64)
         o, lse = res[0], res[1]
         mbits = res[2] if len(res) > 2 else None
         ctx.save_for_backward(qkv, mask if mask is not None else None, o,

@@ -25,6 +25,14 @@ Delta, dV, dK, dQ = 8 executed passes), separate and packed layouts.
 Medians with min..max; TF/s on the executed passes and on the 5 passes
 the result needs (halved work when causal).
 
+--fwd (D = 64): the forward on both arms, alternated round after round in
+one process: the 64-key-stage kernel (fwd64) and the 32-key-tile kernel
+(keys32, what RAVNEST_ATTN_FWD64=0 selects), separate and packed layouts,
+non-causal and causal, with the (B,1,1,S) additive mask BERT passes (all
+zeros) on the non-causal runs. Medians with min..max; TF/s over the two
+matmul passes (halved work when causal). The flagship shape is
+--B 128 --H 12 --S 512.
+
 --decode: cached decoding. Kernel alone: attention_decode against its
 composed torch twin, alternated round after round, at B = 8, 32 x
 (H=12, D=64), (H=16, D=128) x L = 128, 512, 1023 cached keys inside
@@ -243,6 +251,8 @@ def main():
     ap.add_argument("--fill", type=float, nargs="+", default=None,
                     help="live share(s) of a right-padded batch")
     ap.add_argument("--causal", action="store_true")
+    ap.add_argument("--fwd", action="store_true",
+                    help="D=64 forward, 64-key stages against 32-key tiles")
     ap.add_argument("--decode", action="store_true",
                     help="decode attention kernel against its torch twin")
     ap.add_argument("--decode-e2e", action="store_true",
@@ -262,6 +272,10 @@ def main():
         if args.decode_e2e:
             bench_decode_e2e(dev, min(args.rounds, 5))
         return
+    if args.fwd:
+        for causal in (False, True):
+            bench_fwd64(ext, dev, B, S, H, causal, args.rounds, args.iters)
+        return
     if args.fill:
         bench_fill(ext, dev, B, S, H, D, args.fill, args.rounds, args.iters)
         return
@@ -271,6 +285,36 @@ def main():
         return
 
     bench_d64(ext, dev, B, S, H, D, args.causal, args.rounds, args.iters)
+
+
+def bench_fwd64(ext, dev, B, S, H, causal, rounds, iters):
+    D = 64
+    scale = 1.0 / math.sqrt(D)
+    mm = 2 * B * H * S * S * D * (0.5 if causal else 1.0)  # one matmul pass
+    q, k, v = (torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16)
+               for _ in range(3))
+    qkv = torch.randn(B, S, 3, H, D, device=dev, dtype=torch.bfloat16)
+    mask = (torch.Tensor() if causal
+            else torch.zeros(B, 1, 1, S, device=dev))
+    arms = {}
+    for name, flag in (("keys32", False), ("fwd64", True)):
+        arms[f"{name} separate"] = (
+            lambda f=flag: ext.attn_fwd(q, k, v, mask, causal, scale, None,
+                                        f))
+        arms[f"{name} packed"] = (
+            lambda f=flag: ext.attn_fwd_qkv(qkv, mask, causal, scale, 0.0, 0,
+                                            None, None, f))
+    t = {a: [] for a in arms}
+    for _ in range(rounds):
+        for a, fn in arms.items():
+            t[a].append(timeit(fn, iters, 2))
+    print(f"fwd B={B} H={H} S={S} D={D} causal={causal} "
+          f"mask={'none' if causal else 'zeros'}: {rounds} rounds x {iters} "
+          f"iters per arm, arms alternated; ms median [min..max]")
+    for a, x in t.items():
+        med = statistics.median(x)
+        print(f"  fwd {a:16s} {med:8.4f} [{min(x):8.4f}..{max(x):8.4f}] "
+              f"({2 * mm / med / 1e9:6.1f} TF/s)")
 
 
 def bench_d64(ext, dev, B, S, H, D, causal, rounds, iters):
