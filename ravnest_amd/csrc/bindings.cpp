@@ -157,6 +157,14 @@ at::Tensor attn_decode(at::Tensor qkv_new, at::Tensor k_cache,
                        c10::optional<int64_t> max_len,
                        c10::optional<int64_t> n_split);
 int64_t attn_decode_splits(int64_t bh, int64_t max_len);
+at::Tensor attn_varlen_tiles(at::Tensor cu_seqlens, int64_t T);
+std::vector<at::Tensor> attn_varlen_fwd_qkv(at::Tensor qkv,
+                                            at::Tensor cu_seqlens,
+                                            at::Tensor tiles, bool causal,
+                                            double scale);
+at::Tensor attn_varlen_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
+                               at::Tensor lse, at::Tensor cu_seqlens,
+                               at::Tensor tiles, bool causal, double scale);
 at::Tensor mfma_probe(at::Tensor a, at::Tensor b);
 at::Tensor tr16_probe();
 at::Tensor mfma_mx_probe(at::Tensor a, at::Tensor b, int64_t sa, int64_t sb);
@@ -335,6 +343,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_splits", &attn_decode_splits, py::arg("bh"),
         py::arg("max_len"),
         "split count attn_decode picks for B*H heads and max_len keys");
+  m.def("attn_varlen_tiles", &attn_varlen_tiles, py::arg("cu_seqlens"),
+        py::arg("T"),
+        "int32 cu_seqlens (B+1,) -> (T/128 + B + 2, 2) tile table of the "
+        "varlen attention kernels");
+  m.def("attn_varlen_fwd_qkv", &attn_varlen_fwd_qkv, py::arg("qkv"),
+        py::arg("cu_seqlens"), py::arg("tiles"), py::arg("causal"),
+        py::arg("scale"),
+        "varlen flash attention fwd (bf16, D=64): packed (T,3,H,64) qkv -> "
+        "o (T,H,64), lse (H,T)");
+  m.def("attn_varlen_bwd_qkv", &attn_varlen_bwd_qkv, py::arg("qkv"),
+        py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("cu_seqlens"),
+        py::arg("tiles"), py::arg("causal"), py::arg("scale"),
+        "varlen flash attention bwd: packed qkv -> dqkv (T,3,H,64)");
   m.def("mfma_probe", &mfma_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 mapping probe");
   m.def("mfma_mx_probe", &mfma_mx_probe,

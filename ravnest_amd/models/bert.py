@@ -113,16 +113,22 @@ class BertSelfAttention(nn.Module):
             causal=False, prob_dropout=cfg.dropout if exact else 0.0)
         self.out = make_linear(cfg.hidden, cfg.hidden)
 
-    def forward(self, x, mask, out_bias_downstream: bool = False):
+    def forward(self, x, mask, out_bias_downstream: bool = False,
+                cu_seqlens=None, tiles=None):
         """out_bias_downstream: the caller takes the bias gradient of
         self.out from the op that consumes the result (BertLayer.ln1); the
-        projection then runs with its bias detached."""
+        projection then runs with its bias detached. cu_seqlens (+ tiles):
+        x is a packed (T,C) token stream and attention runs within each
+        of its sequences (ops.attention_varlen_qkv); mask is then None."""
         # packed (B,S,3,H,D) qkv: the attention kernel reads the
         # projection's natural layout and returns token-major O — no
         # permute/contiguous copies (unflatten also keeps the fx graph
         # free of .size() scalar nodes)
         qkv = self.qkv(x).unflatten(-1, (3, self.heads, self.head_dim))
-        o = self.core(qkv, mask)
+        if cu_seqlens is not None:
+            o = self.core(qkv, mask, cu_seqlens=cu_seqlens, tiles=tiles)
+        else:
+            o = self.core(qkv, mask)
         if out_bias_downstream:
             return _linear_bias_downstream(self.out, o)
         return self.out(o)
@@ -158,10 +164,17 @@ class BertLayer(nn.Module):
         return (self.fused_bias_grad and torch.is_tensor(a)
                 and _plain_biased_linear(lin) and ln.takes_zbias(a, lin))
 
-    def forward(self, x, mask):
+    def forward(self, x, mask, cu_seqlens=None, tiles=None):
         # attn.out -> ln1 and mlp_out -> ln2: the LayerNorm backward sums
         # dz for the projection's bias (ops/dropout_ln.py zbias)
-        if self._bias_downstream(self.ln1, x, self.attn.out):
+        if cu_seqlens is not None:  # packed (T,C) stream, see BertForMLM
+            kw = dict(cu_seqlens=cu_seqlens, tiles=tiles)
+            if self._bias_downstream(self.ln1, x, self.attn.out):
+                x = self.ln1(x, self.attn(x, None, True, **kw),
+                             zbias=self.attn.out.bias)
+            else:
+                x = self.ln1(x, self.attn(x, None, **kw))
+        elif self._bias_downstream(self.ln1, x, self.attn.out):
             x = self.ln1(x, self.attn(x, mask, out_bias_downstream=True),
                          zbias=self.attn.out.bias)
         else:
@@ -225,26 +238,63 @@ class BertForMLM(nn.Module):
     def forward(self, input_ids, attention_mask):
         return self.head(self._encode(input_ids, attention_mask))
 
+    def _encode_packed(self, ids, pos, cu_seqlens):
+        # Unpadded path: ids, pos (T,) and cu_seqlens from ops.unpad_batch.
+        # Every op but attention is row-wise and runs on the (T,C) live
+        # tokens as it stands; attention stays within each sequence
+        # (ops.attention_varlen_qkv), one tile table for all layers. The
+        # stem is the composed gather + LayerNorm: the fused one indexes
+        # positions from 0 per row of a (B,S) grid.
+        from ..ops import varlen_tiles
+        emb = self.embeddings
+        x = emb.drop(emb.ln(emb.word(ids) + emb.position(pos)))
+        tiles = varlen_tiles(cu_seqlens, ids.shape[0])
+        for layer in self.layers:
+            x = layer(x, None, cu_seqlens=cu_seqlens, tiles=tiles)
+        return x
+
+    def forward_packed(self, ids, pos, cu_seqlens):
+        """Packed ids, pos (T,) and cu_seqlens int32 (B+1,) of
+        ops.unpad_batch, all on the model's device -> logits (T,V). Row t
+        equals forward()'s row of the same token; tail rows carry no
+        information. Eager only: T changes from batch to batch."""
+        return self.head(self._encode_packed(ids, pos, cu_seqlens))
+
+    def forward_loss_packed(self, ids, pos, cu_seqlens, targets, criterion):
+        """forward_loss() on a packed batch: targets (T,) with the tail at
+        criterion.ignore_index. Same conditions, None when they fail."""
+        if not self._sparse_head_applies(ids, targets, criterion):
+            return None
+        from ..ops.mlm_head import sparse_mlm_head_loss
+        dec = self.head.decoder
+        h = self.head.transform(self._encode_packed(ids, pos, cu_seqlens))
+        return sparse_mlm_head_loss(h, dec.weight, dec.bias, targets,
+                                    criterion.ignore_index)
+
+    def _sparse_head_applies(self, input_ids, targets, criterion) -> bool:
+        from ..ops.losses import CrossEntropyLoss
+        from ..ops.mlm_head import (sparse_mlm_head_enabled,
+                                    sparse_mlm_head_supported)
+        dec = self.head.decoder
+        return bool(self.training and sparse_mlm_head_enabled()
+                    and type(criterion) is CrossEntropyLoss
+                    and torch.is_tensor(targets) and input_ids.is_cuda
+                    and dec.weight.is_cuda
+                    and dec.weight.dtype == torch.bfloat16
+                    and not torch.is_autocast_enabled()
+                    and targets.numel() == input_ids.numel()
+                    and sparse_mlm_head_supported(dec.weight, dec.bias,
+                                                  targets))
+
     def forward_loss(self, input_ids, attention_mask, targets, criterion):
         """Opt-in fused model+criterion step: encoder and head transform
         as in forward(), then decoder + cross-entropy on the rows whose
         label is not ignored only (ops/mlm_head.py). Returns the loss, or
         None when the fused op does not apply — the caller then computes
         criterion(self(input_ids, attention_mask), targets)."""
-        from ..ops.losses import CrossEntropyLoss
-        from ..ops.mlm_head import (sparse_mlm_head_enabled,
-                                    sparse_mlm_head_loss,
-                                    sparse_mlm_head_supported)
+        from ..ops.mlm_head import sparse_mlm_head_loss
         dec = self.head.decoder
-        if not (self.training and sparse_mlm_head_enabled()
-                and type(criterion) is CrossEntropyLoss
-                and torch.is_tensor(targets) and input_ids.is_cuda
-                and dec.weight.is_cuda
-                and dec.weight.dtype == torch.bfloat16
-                and not torch.is_autocast_enabled()
-                and targets.numel() == input_ids.numel()):
-            return None
-        if not sparse_mlm_head_supported(dec.weight, dec.bias, targets):
+        if not self._sparse_head_applies(input_ids, targets, criterion):
             return None
         x = self._encode(input_ids, attention_mask)
         h = self.head.transform(x)

@@ -5,7 +5,8 @@ from .activation import (GELU, LinearGelu, Softmax, gelu, bias_gelu,
 from .dropout import Dropout, dropout
 from .dropout_ln import DropoutAddLayerNorm, dropout_add_layer_norm
 from .attention import (AttentionCore, AttentionCoreQKV, attention,
-                        attention_qkv, attention_decode, kv_len_from_mask)
+                        attention_qkv, attention_decode, kv_len_from_mask,
+                        attention_varlen_qkv, varlen_tiles, unpad_batch)
 from .losses import CrossEntropyLoss, cross_entropy
 from .mlm_head import sparse_mlm_head_loss
 from .optim import FusedAdam, FusedSGD, FusedLAMB, clip_grad_norm_
@@ -25,6 +26,7 @@ __all__ = [
     "DropoutAddLayerNorm", "dropout_add_layer_norm",
     "AttentionCore", "AttentionCoreQKV", "attention", "attention_qkv",
     "attention_decode", "kv_len_from_mask",
+    "attention_varlen_qkv", "varlen_tiles", "unpad_batch",
     "CrossEntropyLoss", "cross_entropy", "sparse_mlm_head_loss",
     "FusedAdam", "FusedSGD", "FusedLAMB", "clip_grad_norm_",
     "FusedBatchNorm2d", "FusedBatchNormReLU2d", "FusedBatchNormAddReLU2d",

@@ -40,6 +40,12 @@ exp(-10000 + s - m) == 0). It is off by default: on the all-ones masks of
 the BERT benchmark the twelve extra launches per step buy nothing and
 measured -0.6 % (profiles/attn_kv_len.txt); turn it on for padded data.
 Not for masks whose entries <= -10000 are meant to keep a weight.
+
+Unpadded batches: attention_varlen_qkv runs attention within each
+sequence of a packed (T,3,H,D) token stream given by cu_seqlens, so padded
+query rows cost nothing either (csrc/attention_varlen64.hip: bf16, D=64,
+no mask, kv_len or probability dropout; grids from shapes only, a device
+tile table from varlen_tiles). unpad_batch packs a padded (B,S) batch.
 """
 from __future__ import annotations
 
@@ -321,7 +327,17 @@ class AttentionCoreQKV(nn.Module):
         self.causal = causal
         self.prob_dropout = prob_dropout
 
-    def forward(self, qkv, mask=None, kv_len=None):
+    def forward(self, qkv, mask=None, kv_len=None, cu_seqlens=None,
+                tiles=None):
+        if cu_seqlens is not None:
+            # packed (T,3,H,D) token stream: the lengths are the mask
+            if mask is not None or kv_len is not None \
+                    or self.prob_dropout > 0:
+                raise ValueError(
+                    "cu_seqlens (varlen attention) cannot be combined with "
+                    "mask, kv_len or prob_dropout > 0")
+            return attention_varlen_qkv(qkv, cu_seqlens, causal=self.causal,
+                                        tiles=tiles).flatten(1)
         if self.prob_dropout > 0 and self.training and qkv.is_cuda:
             if qkv.shape[-1] == 64:  # fused philox masks in the kernels
                 return attention_qkv(qkv, mask=mask, causal=self.causal,
@@ -332,6 +348,117 @@ class AttentionCoreQKV(nn.Module):
                 self.training, kv_len)
         return attention_qkv(qkv, mask=mask, causal=self.causal,
                              kv_len=kv_len)
+
+
+def varlen_tiles(cu_seqlens, T):
+    """Tile table of the varlen attention kernels for one packed batch of T
+    rows: int32 (T // 128 + B + 2, 2), built on the device from cu_seqlens
+    (int32 (B+1,)) by one small kernel, no host read. Build it once per
+    batch and hand it to every layer, forward and backward use the same
+    one. None for CPU tensors (the composed twin needs no table)."""
+    if not cu_seqlens.is_cuda:
+        return None
+    return get_ext(required=True).attn_varlen_tiles(cu_seqlens, T)
+
+
+class _AttnVarlenFn(torch.autograd.Function):
+    """Packed varlen path: qkv (T,3,H,64) -> o (T,H,64), per sequence of
+    cu_seqlens (csrc/attention_varlen64.hip)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, tiles, causal, scale):
+        ext = get_ext(required=True)
+        o, lse = ext.attn_varlen_fwd_qkv(qkv, cu_seqlens, tiles, causal,
+                                         scale)
+        ctx.save_for_backward(qkv, o, lse, cu_seqlens, tiles)
+        ctx.causal = causal
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, cu_seqlens, tiles = ctx.saved_tensors
+        dqkv = get_ext(required=True).attn_varlen_bwd_qkv(
+            qkv, o, do.contiguous(), lse, cu_seqlens, tiles, ctx.causal,
+            ctx.scale)
+        return dqkv, None, None, None, None
+
+
+def _varlen_twin(qkv, cu_seqlens, causal, scale):
+    """Composed form of the varlen kernels: every sequence through
+    _math_attention, zeros on the tail. Reads cu_seqlens on the host."""
+    T, _, H, D = qkv.shape
+    cu = cu_seqlens.tolist()
+    outs = []
+    for lo, hi in zip(cu[:-1], cu[1:]):
+        if hi > lo:
+            q, k, v = (qkv[lo:hi, i].transpose(0, 1) for i in range(3))
+            outs.append(_math_attention(q, k, v, None, causal,
+                                        scale).transpose(0, 1))
+    outs.append(qkv.new_zeros(T - cu[-1], H, D))
+    return torch.cat(outs)
+
+
+def attention_varlen_qkv(qkv, cu_seqlens, causal=False, scale=None,
+                         tiles=None):
+    """Attention within each sequence of a packed token stream.
+
+    qkv (T,3,H,D), token-major (the qkv projection of (T,C) activations);
+    cu_seqlens int32 (B+1,) on qkv's device: cu[0] = 0, non-decreasing,
+    cu[B] <= T, sequence b = rows [cu[b], cu[b+1]). Returns o (T,H,D).
+    Rows [cu[B], T) are a tail: their o and dqkv are exact zeros whatever
+    they hold (NaN included), so T may be rounded up. causal puts the
+    diagonal at each sequence's start. No mask, no kv_len, no probability
+    dropout: the lengths are the mask.
+
+    CUDA + bf16 + D == 64 runs csrc/attention_varlen64.hip, whose grids
+    depend on shapes only (nothing reads a length on the host); tiles is
+    varlen_tiles(cu_seqlens, T), built here when not given. Everything
+    else runs the composed twin, which reads cu_seqlens on the host."""
+    if qkv.dim() != 4 or qkv.shape[1] != 3:
+        raise ValueError("qkv must be (T, 3, H, D)")
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 \
+            or cu_seqlens.dtype != torch.int32 \
+            or cu_seqlens.device != qkv.device:
+        raise ValueError("cu_seqlens must be int32 of shape (B+1,) on the "
+                         "device of qkv")
+    D = qkv.shape[-1]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D == 64:
+        if tiles is None:
+            tiles = varlen_tiles(cu_seqlens, qkv.shape[0])
+        return _AttnVarlenFn.apply(qkv.contiguous(), cu_seqlens.contiguous(),
+                                   tiles, causal, scale)
+    return _varlen_twin(qkv, cu_seqlens, causal, scale)
+
+
+def unpad_batch(input_ids, attention_mask, targets=None, multiple=64):
+    """(B,S) padded batch -> packed token stream for the varlen path.
+
+    Meant for the HOST tensors a data loader produces, before the copy to
+    the device (boolean indexing of device tensors would synchronise).
+    Returns (ids (T,), position ids (T,), cu_seqlens int32 (B+1,), targets
+    (T,) or None, T): the tokens with attention_mask != 0 in batch order,
+    their column as position, and T = their count rounded up to
+    `multiple` (at least `multiple`). The tail holds id 0, position 0 and
+    target -100 (the ignore index)."""
+    keep = attention_mask != 0
+    B, S = input_ids.shape
+    lens = keep.sum(1)
+    live = int(lens.sum())
+    T = max(-(-live // multiple), 1) * multiple
+    cu = torch.zeros(B + 1, dtype=torch.int32, device=input_ids.device)
+    cu[1:] = lens.cumsum(0)
+    ids = input_ids.new_zeros(T)
+    ids[:live] = input_ids[keep]
+    pos = input_ids.new_zeros(T)
+    pos[:live] = torch.arange(S, device=input_ids.device).expand(B, S)[keep]
+    tgt = None
+    if targets is not None:
+        tgt = targets.new_full((T,), -100)
+        tgt[:live] = targets[keep]
+    return ids, pos, cu, tgt, T
 
 
 def _decode_twin(qkv_new, k_cache, v_cache, cache_len, scale):

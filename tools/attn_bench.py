@@ -33,6 +33,17 @@ zeros) on the non-causal runs. Medians with min..max; TF/s over the two
 matmul passes (halved work when causal). The flagship shape is
 --B 128 --H 12 --S 512.
 
+--varlen (D = 64): variable-length batches, B sequences inside S. The
+varlen op on the packed (T,3,H,64) stream of the live tokens (T rounded up
+to 64, one tile table per batch) against the packed kernels with kv_len on
+the padded (B,S,3,H,64) batch and against the same kernels on the dense
+batch, alternated round after round in one process; fwd and fwd+bwd.
+Lengths: the seeded uniform [16, S] draw of examples/bert/provider.py
+--var-len, a 25 % fill and a 100 % fill. Medians with min..max and the
+work ratio sum(len^2) / (B S^2) next to each. A build without the varlen
+entry points runs the other two arms only (the parent-commit run). The
+flagship shape is --B 128 --H 12 --S 512.
+
 --decode: cached decoding. Kernel alone: attention_decode against its
 composed torch twin, alternated round after round, at B = 8, 32 x
 (H=12, D=64), (H=16, D=128) x L = 128, 512, 1023 cached keys inside
@@ -130,6 +141,63 @@ def bench_fill(ext, dev, B, S, H, D, fills, rounds, iters):
                     f"{d} {med:7.3f} [{min(x):7.3f}..{max(x):7.3f}] "
                     f"({nmm * full_mm * useful / med / 1e9:6.1f} useful TF/s)")
             print(f"  {m:13s} " + "  ".join(parts))
+
+
+def bench_varlen(ext, dev, B, S, H, rounds, iters):
+    D, empty = 64, torch.Tensor()
+    scale = 1.0 / math.sqrt(D)
+    g = torch.Generator().manual_seed(42)
+    draws = {"uniform[16,S]": torch.randint(16, S + 1, (B,), generator=g),
+             "fill 0.25": draw_lengths(B, S, 0.25).long(),
+             "fill 1.00": torch.full((B,), S)}
+    has_varlen = hasattr(ext, "attn_varlen_fwd_qkv")
+    print(f"varlen against padded, B={B} S={S} H={H} D={D}; {rounds} rounds "
+          f"x {iters} iters per arm, arms alternated; ms median [min..max]")
+    for name, lens in draws.items():
+        live = int(lens.sum())
+        T = -(-live // 64) * 64
+        ratio = float((lens.double() ** 2).sum()) / (B * S * S)
+        qkv = torch.randn(B, S, 3, H, D, device=dev, dtype=torch.bfloat16)
+        do = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
+        keep = (torch.arange(S)[None, :] < lens[:, None]).to(dev)
+        pqkv = torch.zeros(T, 3, H, D, device=dev, dtype=torch.bfloat16)
+        pdo = torch.zeros(T, H, D, device=dev, dtype=torch.bfloat16)
+        pqkv[:live], pdo[:live] = qkv[keep], do[keep]
+        kvl = lens.to(device=dev, dtype=torch.int32)
+        cu = torch.zeros(B + 1, dtype=torch.int32)
+        cu[1:] = lens.cumsum(0)
+        cu = cu.to(dev)
+
+        def padded(kv, bwd):
+            o, lse = ext.attn_fwd_qkv(qkv, empty, False, scale, 0.0, 0, None,
+                                      kv)
+            if bwd:
+                ext.attn_bwd_qkv(qkv, o, do, lse, empty, False, scale, 0.0,
+                                 None, kv)
+
+        def varlen(bwd):
+            o, lse = ext.attn_varlen_fwd_qkv(pqkv, cu, tiles, False, scale)
+            if bwd:
+                ext.attn_varlen_bwd_qkv(pqkv, o, pdo, lse, cu, tiles, False,
+                                        scale)
+
+        arms = {"dense": lambda b: padded(None, b),
+                "kv_len": lambda b: padded(kvl, b)}
+        if has_varlen:
+            tiles = ext.attn_varlen_tiles(cu, T)
+            arms["varlen"] = varlen
+        t = {(a, b): [] for a in arms for b in (False, True)}
+        for _ in range(rounds):
+            for a, fn in arms.items():
+                for b in (False, True):
+                    t[(a, b)].append(timeit(lambda: fn(b), iters, 3))
+        print(f"{name}: live tokens {live} of {B * S} (T = {T}), work ratio "
+              f"sum(len^2)/(B S^2) = {ratio:.3f}")
+        for a in arms:
+            print(f"  {a:7s} " + "  ".join(
+                f"{lab} {statistics.median(x):7.3f} "
+                f"[{min(x):7.3f}..{max(x):7.3f}]" for lab, x in
+                (("fwd", t[(a, False)]), ("fwd+bwd", t[(a, True)]))))
 
 
 def bench_d128(ext, dev, B, S, H, D, causal, rounds, iters):
@@ -253,6 +321,8 @@ def main():
     ap.add_argument("--causal", action="store_true")
     ap.add_argument("--fwd", action="store_true",
                     help="D=64 forward, 64-key stages against 32-key tiles")
+    ap.add_argument("--varlen", action="store_true",
+                    help="D=64 varlen op against kv_len on the padded batch")
     ap.add_argument("--decode", action="store_true",
                     help="decode attention kernel against its torch twin")
     ap.add_argument("--decode-e2e", action="store_true",
@@ -271,6 +341,9 @@ def main():
             bench_decode(ext, dev, args.rounds, args.iters)
         if args.decode_e2e:
             bench_decode_e2e(dev, min(args.rounds, 5))
+        return
+    if args.varlen:
+        bench_varlen(ext, dev, B, S, H, args.rounds, args.iters)
         return
     if args.fwd:
         for causal in (False, True):

@@ -8,6 +8,9 @@ Delta from that bf16 o, P and dS rounded to bf16 before their matmuls,
 bf16 outputs. Not modelled: __expf and the order of the fp32 sums.
 
 Usage: python tools/attn_bwd_round_model.py   (no GPU needed)
+       python tools/attn_bwd_round_model.py --varlen
+           the same model per sequence on the cases of
+           tests/attn_varlen_cases.py (bound of test_attn_varlen_gpu.py)
 """
 import os
 import sys
@@ -21,8 +24,12 @@ import test_attn_bwd64_gpu as t  # noqa: E402
 
 
 def model(name, q, k, v, do, mask):
+    return model_add(q, k, v, do,
+                     t.additive_terms(name, mask, q.device).float())
+
+
+def model_add(q, k, v, do, add):
     bf = lambda x: x.to(torch.bfloat16).float()  # noqa: E731
-    add = t.additive_terms(name, mask, q.device).float()
     qf, kf, vf, dof = (x.float() for x in (q, k, v, do))
     s = qf @ kf.transpose(-2, -1) * t.SCALE + add
     lse = torch.logsumexp(s, dim=-1, keepdim=True)
@@ -49,5 +56,24 @@ def main():
     print(f"worst figure {worst:.4f}; bound = 3 x worst = {3 * worst:.4f}")
 
 
+def main_varlen():
+    import attn_varlen_cases as vc
+    worst = 0.0
+    for name in vc.CASES:
+        for causal in (False, True):
+            qkv, do, cu = vc.make_inputs(name, 0)
+            errs = [0.0, 0.0, 0.0]
+            for (q, k, v, g), ref in zip(vc.sequences(qkv, do, cu),
+                                         vc.reference(qkv, do, cu, causal)):
+                add = vc.causal_term(q.shape[1], causal).float()
+                got = model_add(q, k, v, g, add)
+                errs = [max(e, vc.rel_err(x, r))
+                        for e, x, r in zip(errs, got, ref[2:])]
+            worst = max(worst, *errs)
+            print(f"{name:6s} causal={causal:d} " + "  ".join(
+                f"{lab} {e:.4f}" for lab, e in zip(("dq", "dk", "dv"), errs)))
+    print(f"worst figure {worst:.4f}; bound = 3 x worst = {3 * worst:.4f}")
+
+
 if __name__ == "__main__":
-    main()
+    main_varlen() if "--varlen" in sys.argv[1:] else main()
