@@ -58,6 +58,10 @@ at::Tensor mx_gemm(at::Tensor x, at::Tensor xs, at::Tensor w,
                    at::Tensor ws, c10::optional<at::Tensor> bias);
 at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
                     at::Tensor ws, c10::optional<at::Tensor> bias);
+at::Tensor mx_gemm2_splitk(at::Tensor xq, at::Tensor xs, at::Tensor wq,
+                           at::Tensor ws, c10::optional<int64_t> n_split);
+std::vector<at::Tensor> mx_quant_t(at::Tensor x);
+std::vector<at::Tensor> mx_quant_dual(at::Tensor x);
 at::Tensor mx_scale_probe(at::Tensor a, at::Tensor b, at::Tensor sa,
                           at::Tensor sb);
 at::Tensor softmax_fwd(at::Tensor x);
@@ -248,6 +252,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "LDS-staged MX fp8 GEMM (256^2 4-phase, scaled 32x32x64 MFMA)",
         py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"),
         py::arg("bias") = py::none());
+  m.def("mx_gemm2_splitk", &mx_gemm2_splitk,
+        "mx_gemm2 with the contraction split over the grid: fp32 partials "
+        "per split, summed in index order; n_split = None fills the "
+        "machine, every split needs >= 2 K-tiles of 128",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"),
+        py::arg("n_split") = py::none());
+  m.def("mx_quant_t", &mx_quant_t,
+        "bf16 (R, C) -> MX fp8 of x^T: [qt (C, Rp), st (C, Rp/32)], "
+        "Rp = max(256, round_up(R, 128)), zero padding");
+  m.def("mx_quant_dual", &mx_quant_dual,
+        "one pass: [q, s] = mx_quant(x) and [qt, st] = mx_quant_t(x); "
+        "C % 32 == 0");
   m.def("mx_scale_probe", &mx_scale_probe,
         "per-lane scale-byte semantics probe");
   m.def("softmax_fwd", &softmax_fwd, "standalone softmax fwd (last dim)");

@@ -104,7 +104,14 @@ DEVINL float bias_val(const u16x4& b, int v) { return us2f(b[v]); }
 // bf16(float(bf16(acc)) + bias[n]): the two roundings of a separate bf16
 // add after the GEMM, so fusing it changes no bit. The K-loop is the same
 // in every instantiation.
-template <typename BT>
+//
+// SPLIT: the grid is (output tiles) x (nsplit). Block (tile, ksp) runs the
+// same K-loop over the contiguous K-tiles [kt0, kt0 + nKT) of its split
+// (whole 128-element tiles, >= 2 so the prologue's double buffer holds;
+// the first nKTall % nsplit splits take one more) and stores its fp32
+// accumulators to WSP[ksp][M][N]; mx2_reduce sums the splits in index
+// order and rounds once. tpb is 1 and there is no bias.
+template <typename BT, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void mx2_kernel(
     const unsigned char* __restrict__ XQ,
     const unsigned char* __restrict__ XS_T,
@@ -112,16 +119,23 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
     const unsigned char* __restrict__ WS_T,
     const BT* __restrict__ bias,
     bf16_t* __restrict__ C, long M, long N, long K, long Mp, long Np,
-    int MT, int NTb, int tpb) {
+    int MT, int NTb, int tpb, float* __restrict__ WSP = nullptr,
+    int nsplit = 1) {
   __shared__ char smem[2 * BUF_FULL];
 
-  const int nwg = MT * NTb;
+  const int nwg = SPLIT ? MT * NTb * nsplit : MT * NTb;
   int bid = blockIdx.x, wg;
   if ((nwg & 7) == 0) {
     wg = (bid & 7) * (nwg >> 3) + (bid >> 3);
   } else {
     const int q = nwg >> 3, r = nwg & 7, x = bid & 7, lin = bid >> 3;
     wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + lin;
+  }
+  // the splits of one tile are neighbours under the XCD remap
+  int ksp = 0;
+  if constexpr (SPLIT) {
+    ksp = wg % nsplit;
+    wg /= nsplit;
   }
   constexpr int GM = 8;
   const int group = wg / (GM * NTb);
@@ -138,7 +152,12 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
 
   const long mBase = (long)bm * BM;
   const long nBase = (long)bn0 * BN;
-  const int nKT = (int)(K / BKE);
+  int nKT = (int)(K / BKE), kt0 = 0;
+  if constexpr (SPLIT) {
+    const int q = nKT / nsplit, r = nKT % nsplit;
+    kt0 = ksp * q + min(ksp, r);
+    nKT = q + (ksp < r ? 1 : 0);
+  }
   const unsigned SJ = (unsigned)(BN * K);  // bytes per column tile of W
 
   unsigned sp[4][2];
@@ -158,7 +177,7 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
       jj = tpb - 1;
       tt = nKT - 1;
     }
-    const unsigned off = (unsigned)tt * BKE;
+    const unsigned off = (unsigned)(kt0 + tt) * BKE;
     const int b = (jj * nKT + tt) & 1;
     char* const lb = smem + b * BUF_FULL + slo[kind] + wbase;
     const char* const base =
@@ -196,14 +215,15 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
     if (wid == 0) {
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)(
-              XS_T + (long)tt * Mp * 4 + mBase * 4 + lane * 16),
+              XS_T + (long)(kt0 + tt) * Mp * 4 + mBase * 4 + lane * 16),
           (__attribute__((address_space(3))) void*)(
               smem + b * BUF_FULL + BUF_BYTES),
           16, 0, 0);
     } else if (wid == 1) {
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)(
-              WS_T + (long)tt * Np * 4 + (nBase + (long)jj * BN) * 4 +
+              WS_T + (long)(kt0 + tt) * Np * 4 +
+              (nBase + (long)jj * BN) * 4 +
               lane * 16),
           (__attribute__((address_space(3))) void*)(
               smem + b * BUF_FULL + BUF_BYTES + 1024),
@@ -384,6 +404,19 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
       for (int qd = 0; qd < 4; ++qd) {
         const long n = nCol0 + nf * 32 + qd * 8;
         if (n >= N) continue;
+        if constexpr (SPLIT) {
+          // n % 4 == 0: 16 B stores when the row pitch keeps them aligned
+          float* const w = WSP + ((long)ksp * M + m) * N + n;
+          if (n + 4 <= N && (N & 3) == 0) {
+            *reinterpret_cast<f32x4*>(w) =
+                f32x4{acc[mf][nf][4 * qd + 0], acc[mf][nf][4 * qd + 1],
+                      acc[mf][nf][4 * qd + 2], acc[mf][nf][4 * qd + 3]};
+          } else {
+            for (int v = 0; v < 4; ++v)
+              if (n + v < N) w[v] = acc[mf][nf][4 * qd + v];
+          }
+          continue;
+        }
         u16x4 o{f2us(acc[mf][nf][4 * qd + 0]),
                 f2us(acc[mf][nf][4 * qd + 1]),
                 f2us(acc[mf][nf][4 * qd + 2]),
@@ -408,10 +441,47 @@ __global__ __launch_bounds__(512, 2) void mx2_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// C[i] = bf16(sum over splits, in index order, of WSP[p][i]): the same one
+// rounding as mx2_kernel's own epilogue, so one split gives its bits.
+// V = 4 needs MN % 4 == 0.
+#if defined(__HIP_DEVICE_COMPILE__)
+// no packed fp32 VALU ops in the new kernel
+#define MX2R_TARGET __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MX2R_TARGET
+#endif
+template <int V>
+MX2R_TARGET __global__ __launch_bounds__(256) void mx2_reduce(
+    const float* __restrict__ WSP, bf16_t* __restrict__ C, long MN,
+    int nsplit) {
+  using vec = std::conditional_t<V == 4, f32x4, float>;
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * V;
+  if (i >= MN) return;
+  vec s = *reinterpret_cast<const vec*>(WSP + i);
+  for (int p = 1; p < nsplit; ++p) {
+    const vec t = *reinterpret_cast<const vec*>(WSP + p * MN + i);
+    if constexpr (V == 4) {
+      s[0] += t[0]; s[1] += t[1]; s[2] += t[2]; s[3] += t[3];
+    } else {
+      s += t;
+    }
+  }
+  unsigned short* const c = reinterpret_cast<unsigned short*>(C) + i;
+  if constexpr (V == 4) {
+    *reinterpret_cast<u16x4*>(c) =
+        u16x4{f2us(s[0]), f2us(s[1]), f2us(s[2]), f2us(s[3])};
+  } else {
+    c[0] = f2us(s);
+  }
+}
+
 }  // namespace
 
-at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
-                    at::Tensor ws, c10::optional<at::Tensor> bias) {
+namespace {
+
+// the operand checks shared by mx_gemm2 and mx_gemm2_splitk
+void check_operands(const at::Tensor& xq, const at::Tensor& xs,
+                    const at::Tensor& wq, const at::Tensor& ws) {
   TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kByte &&
                   xq.is_contiguous() && xq.dim() >= 1,
               "mx_gemm2: xq must be a contiguous uint8 (e4m3) GPU tensor");
@@ -423,8 +493,8 @@ at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
   TORCH_CHECK(wq.size(1) == K, "mx_gemm2: K mismatch");
   TORCH_CHECK(K % BKE == 0 && K >= 2 * BKE,
               "mx_gemm2: K % 128 == 0 and K >= 256 required");
+  TORCH_CHECK(xq.numel() >= 1 && wq.size(0) >= 1, "mx_gemm2: empty operand");
   const long M = xq.numel() / K, N = wq.size(0);
-  TORCH_CHECK(M >= 1 && N >= 1, "mx_gemm2: empty operand");
   TORCH_CHECK(xq.numel() < (1ll << 32) && wq.numel() < (1ll << 32),
               "mx_gemm2: operands must be < 4 GiB (32-bit staging offsets)");
   TORCH_CHECK(xs.is_cuda() && ws.is_cuda() &&
@@ -434,6 +504,29 @@ at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
   TORCH_CHECK(xs.is_contiguous() && ws.is_contiguous() &&
                   xs.numel() == M * (K / 32) && ws.numel() == N * (K / 32),
               "mx_gemm2: scales must be contiguous (rows, K/32)");
+}
+
+// tile-major scale repack for the kernel's glds staging: (rows, K/32)
+// u8 -> (nKT, rowsPadded) u32 (one u32 = the 4 MX-block exponents of
+// one row's 128-element K-tile), rows zero-padded to the 256 grid
+// (e8m0 0x00 = 2^-127: pad rows contribute ~0 and their outputs are
+// dropped by the epilogue bounds checks anyway).
+at::Tensor pack_scales(const at::Tensor& sc, long rows, long rowsP,
+                       long nKT) {
+  auto t = at::zeros({nKT, rowsP}, sc.options().dtype(at::kInt));
+  t.narrow(1, 0, rows).copy_(
+      sc.reshape({rows, nKT, 4}).view(at::kInt).reshape({rows, nKT})
+          .transpose(0, 1));
+  return t;
+}
+
+}  // namespace
+
+at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
+                    at::Tensor ws, c10::optional<at::Tensor> bias) {
+  check_operands(xq, xs, wq, ws);
+  const long K = xq.size(-1);
+  const long M = xq.numel() / K, N = wq.size(0);
   if (bias.has_value())
     TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
                     bias->numel() == N &&
@@ -455,22 +548,9 @@ at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
     }
   }
   const int NTb = NT / tpb;
-  // tile-major scale repack for the kernel's glds staging: (rows, K/32)
-  // u8 -> (nKT, rowsPadded) u32 (one u32 = the 4 MX-block exponents of
-  // one row's 128-element K-tile), rows zero-padded to the 256 grid
-  // (e8m0 0x00 = 2^-127: pad rows contribute ~0 and their outputs are
-  // dropped by the epilogue bounds checks anyway).
   const long nKT = K / BKE, Mp = (long)MT * BM, Np = (long)NT * BN;
-  auto iopt = xq.options().dtype(at::kInt);
-  auto pack = [&](const at::Tensor& sc, long rows, long rowsP) {
-    auto t = at::zeros({nKT, rowsP}, iopt);
-    t.narrow(1, 0, rows).copy_(
-        sc.reshape({rows, nKT, 4}).view(at::kInt).reshape({rows, nKT})
-            .transpose(0, 1));
-    return t;
-  };
-  auto xs_t = pack(xs, M, Mp);
-  auto ws_t = pack(ws, N, Np);
+  auto xs_t = pack_scales(xs, M, Mp, nKT);
+  auto ws_t = pack_scales(ws, N, Np, nKT);
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   dim3 grid((unsigned)(MT * NTb)), block(512);
 #define LAUNCH_MX2(BT, BP)                                                  \
@@ -488,6 +568,56 @@ at::Tensor mx_gemm2(at::Tensor xq, at::Tensor xs, at::Tensor wq,
   else
     LAUNCH_MX2(bf16_t, reinterpret_cast<const bf16_t*>(bias->data_ptr()));
 #undef LAUNCH_MX2
+  HIP_CHECK_LAST();
+  return C;
+}
+
+// The same product with the contraction split over the grid, for outputs
+// too small to fill the machine (the weight gradient: few tiles, K = all
+// the rows). Deterministic: fixed ranges, fixed summation order.
+at::Tensor mx_gemm2_splitk(at::Tensor xq, at::Tensor xs, at::Tensor wq,
+                           at::Tensor ws, c10::optional<int64_t> n_split) {
+  check_operands(xq, xs, wq, ws);
+  const long K = xq.size(-1);
+  const long M = xq.numel() / K, N = wq.size(0);
+  const long nKT = K / BKE;
+  const int MT = (int)((M + BM - 1) / BM), NT = (int)((N + BN - 1) / BN);
+  const long tiles = (long)MT * NT;
+  // one block per CU (LDS) on 256 CUs: the largest count that keeps the
+  // grid within one wave of blocks and every split at >= 2 K-tiles
+  const long nsplit = n_split.has_value()
+      ? *n_split
+      : std::max<long>(1, std::min<long>(256 / tiles, nKT / 2));
+  TORCH_CHECK(nsplit >= 1 && nKT / nsplit >= 2,
+              "mx_gemm2_splitk: every split needs >= 2 K-tiles of 128 (K = ",
+              K, ", n_split = ", nsplit, ")");
+  TORCH_CHECK(tiles * nsplit <= 0x7FFFFFFFl,
+              "mx_gemm2_splitk: grid too large");
+  const long Mp = (long)MT * BM, Np = (long)NT * BN, MN = M * N;
+  auto xs_t = pack_scales(xs, M, Mp, nKT);
+  auto ws_t = pack_scales(ws, N, Np, nKT);
+  auto wsp = at::empty({nsplit, M, N}, xq.options().dtype(at::kFloat));
+  auto C = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
+  auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  hipLaunchKernelGGL((mx2_kernel<void, true>),
+                     dim3((unsigned)(tiles * nsplit)), dim3(512), 0, stream,
+                     xq.data_ptr<unsigned char>(),
+                     reinterpret_cast<unsigned char*>(xs_t.data_ptr<int>()),
+                     wq.data_ptr<unsigned char>(),
+                     reinterpret_cast<unsigned char*>(ws_t.data_ptr<int>()),
+                     (const void*)nullptr,
+                     reinterpret_cast<bf16_t*>(C.data_ptr()), M, N, K, Mp,
+                     Np, MT, NT, 1, wsp.data_ptr<float>(), (int)nsplit);
+  HIP_CHECK_LAST();
+  auto* cp = reinterpret_cast<bf16_t*>(C.data_ptr());
+  if (MN % 4 == 0)
+    hipLaunchKernelGGL((mx2_reduce<4>),
+                       dim3((unsigned)((MN / 4 + 255) / 256)), dim3(256), 0,
+                       stream, wsp.data_ptr<float>(), cp, MN, (int)nsplit);
+  else
+    hipLaunchKernelGGL((mx2_reduce<1>), dim3((unsigned)((MN + 255) / 256)),
+                       dim3(256), 0, stream, wsp.data_ptr<float>(), cp, MN,
+                       (int)nsplit);
   HIP_CHECK_LAST();
   return C;
 }

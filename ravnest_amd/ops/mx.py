@@ -2,9 +2,23 @@
 
 Forward quantizes activations and weights to e4m3 with per-32-element
 e8m0 block scales and runs `mfma_scale_f32_32x32x64_f8f6f4` (2x the bf16
-MFMA rate, csrc/mx.hip). Backward stays bf16 (dX = dY @ W, dW = dY^T @ X
-— standard fp8-training recipe: low-precision forward, higher-precision
-gradients). CPU / non-multiple-of-64 shapes fall back to a plain matmul.
+MFMA rate, csrc/mx.hip). By default the backward stays bf16 (dX = dY @ W,
+dW = dY^T @ X — standard fp8-training recipe: low-precision forward,
+higher-precision gradients). CPU / non-multiple-of-64 shapes fall back to a
+plain matmul.
+
+fp8 backward (FP8_BACKWARD, off by default; RAVNEST_MX_BWD=1, or
+fp8_backward=True per layer / call): both gradient GEMMs run on the
+block-scaled MFMA too. Their MX blocks must lie along the contraction,
+which is the strided axis of dy, x and the weight, so a transposing
+quantiser (csrc/mx_quant_t.hip) produces them:
+    dyq, dys, dyqt, dyst = mx_quant_dual(dy)        one read of dy
+    dx = gemm(dyq, dys, *mx_quant_t(weight))        contraction out_features
+    dw = mx_gemm2_splitk(dyqt, dyst, *mx_quant_t(x))   contraction rows
+db is unchanged. Only the bf16 x and weight are saved, as before. A layer
+takes this path when fp8_backward_eligible() holds (out_features % 64 == 0
+and every operand under 2^32 elements); any other takes the bf16 backward.
+It changes the gradients by e4m3's rounding of dy, x and the weight.
 
 Fused quantisation (FUSED_QUANT, on by default): a producer that has the
 activation in registers (FusedLayerNorm / LinearGelu built with
@@ -27,6 +41,9 @@ from ._ext import get_ext
 
 # read at call time by the producers and by mx_linear
 FUSED_QUANT = os.environ.get("RAVNEST_FUSED_MX_QUANT", "1") != "0"
+
+# read at call time by mx_linear; fp8_backward=None follows it
+FP8_BACKWARD = os.environ.get("RAVNEST_MX_BWD", "0") == "1"
 
 _TAG = "_ravnest_mx"
 
@@ -56,9 +73,47 @@ def take_mx(x: torch.Tensor):
     return q, s
 
 
+def _contraction_pad(n: int) -> int:
+    """Rows of mx_quant_t's output: max(256, round_up(n, 128))."""
+    return max(256, -(-n // 128) * 128)
+
+
+def fp8_backward_eligible(rows: int, in_features: int,
+                          out_features: int) -> bool:
+    """Whether the fp8 backward serves a (rows, in) x (out, in) layer.
+
+    dgrad contracts over out_features with dy's row-blocked quantisation,
+    whose width is out_features itself: mx_gemm2 needs out % 128 == 0 and
+    out >= 256, mx_gemm out % 64 == 0 (mx_quant_dual's own out % 32 == 0
+    follows). wgrad contracts over the padded rows, which always satisfy
+    mx_gemm2_splitk. Every quantised operand stays under 2^32 elements
+    (32-bit staging offsets)."""
+    if rows < 1 or out_features % 64 != 0:
+        return False
+    rp, op = _contraction_pad(rows), _contraction_pad(out_features)
+    return max(rows * out_features, out_features * rp, in_features * rp,
+               in_features * op) < 2 ** 32
+
+
+def _fp8_backward(ext, d2, x2, weight):
+    """-> dx (rows, in), dw (out, in), both bf16."""
+    out = d2.shape[1]
+    dyq, dys, dyqt, dyst = ext.mx_quant_dual(d2)
+    wqt, wst = ext.mx_quant_t(weight.contiguous())      # (in, pad(out))
+    if wqt.shape[1] == out:
+        dx = ext.mx_gemm2(dyq, dys, wqt, wst)
+    else:
+        # the padding columns are not part of dy's contraction
+        dx = ext.mx_gemm(dyq, dys, wqt[:, :out].contiguous(),
+                         wst[:, :out // 32].contiguous())
+    del dyq, dys, wqt, wst
+    xqt, xst = ext.mx_quant_t(x2)                       # (in, pad(rows))
+    return dx, ext.mx_gemm2_splitk(dyqt, dyst, xqt, xst)
+
+
 class _MXLinearFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, xqs=None):
+    def forward(ctx, x, weight, bias, xqs=None, fp8_bwd=False):
         ext = get_ext(required=True)
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).contiguous()
@@ -84,25 +139,35 @@ class _MXLinearFn(torch.autograd.Function):
             y = y + bias
         ctx.save_for_backward(x2, weight)
         ctx.has_bias = bias is not None
+        ctx.fp8_bwd = fp8_bwd
         return y.reshape(*shp[:-1], weight.size(0))
 
     @staticmethod
     def backward(ctx, dy):
         x2, weight = ctx.saved_tensors
         d2 = dy.reshape(-1, dy.shape[-1])
+        db = d2.sum(0) if ctx.has_bias else None
+        if ctx.fp8_bwd and d2.dtype == torch.bfloat16 and \
+                weight.dtype == torch.bfloat16 and \
+                fp8_backward_eligible(d2.shape[0], *weight.shape[::-1]):
+            dx, dw = _fp8_backward(get_ext(required=True), d2.contiguous(),
+                                   x2, weight)
+            return dx.reshape(*dy.shape[:-1], weight.size(1)), dw, db, \
+                None, None
         dx = (d2 @ weight).reshape(*dy.shape[:-1], weight.size(1))
         dw = d2.t() @ x2
-        db = d2.sum(0) if ctx.has_bias else None
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def mx_linear(x, weight, bias=None):
+def mx_linear(x, weight, bias=None, fp8_backward=None):
+    """fp8_backward: None follows FP8_BACKWARD; True / False override it."""
     if x.is_cuda and x.dtype == torch.bfloat16 and \
             x.size(-1) % 64 == 0 and x.size(-1) == weight.size(1):
         # the tag is consumed even with the switch off (it is then stale)
         xqs = take_mx(x)
-        return _MXLinearFn.apply(x, weight, bias,
-                                 xqs if FUSED_QUANT else None)
+        return _MXLinearFn.apply(
+            x, weight, bias, xqs if FUSED_QUANT else None,
+            FP8_BACKWARD if fp8_backward is None else bool(fp8_backward))
     return torch.nn.functional.linear(x, weight, bias)
 
 
@@ -110,13 +175,17 @@ class MXLinear(nn.Module):
     """Drop-in nn.Linear running the MX fp8 forward path on GPU.
 
     State-dict compatible with nn.Linear (weight/bias stay bf16 masters;
-    quantization happens on the fly per forward).
+    quantization happens on the fly per forward). fp8_backward: None
+    follows ops.mx.FP8_BACKWARD at call time; True / False fix the choice
+    for this layer (see the module docstring for which shapes it serves).
     """
 
     _is_leaf_module = True  # fx: device-dependent dispatch
 
-    def __init__(self, in_features: int, out_features: int, bias: bool = True):
+    def __init__(self, in_features: int, out_features: int, bias: bool = True,
+                 fp8_backward=None):
         super().__init__()
+        self.fp8_backward = fp8_backward
         self.in_features = in_features
         self.out_features = out_features
         self.weight = nn.Parameter(torch.empty(out_features, in_features))
@@ -124,7 +193,7 @@ class MXLinear(nn.Module):
         nn.init.normal_(self.weight, std=0.02)
 
     def forward(self, x):
-        return mx_linear(x, self.weight, self.bias)
+        return mx_linear(x, self.weight, self.bias, self.fp8_backward)
 
     @classmethod
     def from_linear(cls, lin: nn.Linear) -> "MXLinear":
