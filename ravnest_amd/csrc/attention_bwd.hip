@@ -592,9 +592,20 @@ std::vector<at::Tensor> attn_bwd_impl(
     StridesB sdo, StridesB sg, bf16_t* dqb, bf16_t* dkb, bf16_t* dvb,
     const at::TensorOptions& fopt, const int* kvl, int D,
     c10::optional<bool> bwd64, float pdrop = 0.f,
-    const unsigned* mbits = nullptr) {
+    const unsigned* mbits = nullptr,
+    c10::optional<at::Tensor> delta_buf = c10::nullopt) {
   const float inv_keep = 1.f / (1.f - pdrop);
-  auto delta = at::empty({B * H * (long)S}, fopt);
+  // Delta scratch; a caller that wants to read it hands the buffer in
+  at::Tensor delta;
+  if (delta_buf.has_value()) {
+    delta = *delta_buf;
+    TORCH_CHECK(delta.is_cuda() && delta.is_contiguous() &&
+                    delta.scalar_type() == at::kFloat &&
+                    delta.numel() == B * H * (long)S,
+                "attn_bwd: delta must be contiguous fp32 of B*H*S");
+  } else {
+    delta = at::empty({B * H * (long)S}, fopt);
+  }
   auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   if (D == 128) {
     TORCH_CHECK(pdrop == 0.f,
@@ -674,7 +685,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor lse, at::Tensor mask, bool causal,
                                  double scale,
                                  c10::optional<at::Tensor> kv_len,
-                                 c10::optional<bool> bwd64) {
+                                 c10::optional<bool> bwd64,
+                                 c10::optional<at::Tensor> delta) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
               v.is_contiguous() && o.is_contiguous());
   TORCH_CHECK(q.scalar_type() == at::kBFloat16);
@@ -704,7 +716,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                 reinterpret_cast<bf16_t*>(dk.data_ptr()),
                 reinterpret_cast<bf16_t*>(dv.data_ptr()),
                 q.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B), D,
-                bwd64);
+                bwd64, 0.f, nullptr, delta);
   return {dq, dk, dv};
 }
 
@@ -714,7 +726,8 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         double scale, double pdrop,
                         c10::optional<at::Tensor> mbits,
                         c10::optional<at::Tensor> kv_len,
-                        c10::optional<bool> bwd64) {
+                        c10::optional<bool> bwd64,
+                        c10::optional<at::Tensor> delta) {
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && o.is_contiguous());
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3);
   const long B = qkv.size(0), H = qkv.size(3);
@@ -745,6 +758,6 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                 mask_ptr, has_mask, causal, scale, B, H, S, sp, sod, sp,
                 dbase, dbase + HD, dbase + 2 * HD,
                 qkv.options().dtype(at::kFloat), attn_kv_len_ptr(kv_len, B),
-                D, bwd64, (float)pdrop, mb);
+                D, bwd64, (float)pdrop, mb, delta);
   return dqkv;
 }

@@ -16,7 +16,12 @@
 //   dq: S^T, dP^T (8) -> dS^T -> dQ += dS K (4), twice = 24 per barrier,
 // against 12 in the 32-row kernels. One S matmul and one staging of Q/dO
 // feed both dK and dV, so the backward executes 7 matmul passes, not 8,
-// in 3 launches (Delta, kv, dq), not 4. When both sub-tiles of a stage are
+// in 3 launches (Delta, kv, dq), not 4. RAVNEST_ATTN_DELTA_FUSED=1 (read at
+// every call) makes it 2 (dq, kv), with Delta computed by the dq kernel from
+// its dO fragments: the Delta kernel's pass over dO and O (200 MB at
+// BERT-base's shape for 4 bytes per row) becomes one O read by the waves
+// that hold dO already. Off by default: the BERT step gained 0.3 %, inside
+// the run-to-run spread (profiles/residual_delta.txt). When both sub-tiles of a stage are
 // live their S/dP matmuls are issued together ahead of the first exp
 // phase, so one sub-tile's MFMAs cover the other's LDS-read -> exp -> pack
 // chain inside one wave as well as across waves.
@@ -65,20 +70,25 @@ BWD64_TARGET __global__ __launch_bounds__(256, 2) void attn_bwd64_kv_kernel(
                  causal, scale, has_mask, sio.rs, sdo.rs, sg.rs);
 }
 
+// DELTA: o is read and delta written (bwd64_dq_block); else o is unused
+template <bool DELTA>
 BWD64_TARGET __global__ __launch_bounds__(256, 2) void attn_bwd64_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
-    const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    const float* __restrict__ mask, bf16_t* __restrict__ dq, int S,
+    const bf16_t* __restrict__ v, const bf16_t* __restrict__ o,
+    const bf16_t* __restrict__ dout, const float* __restrict__ lse,
+    float* __restrict__ delta, const float* __restrict__ mask,
+    bf16_t* __restrict__ dq, int S,
     int causal, float scale, int has_mask, long H, StridesB sio,
     StridesB sdo, StridesB sg, const int* __restrict__ kv_len) {
   const long bh = blockIdx.y;
   const long b = bh / H, h = bh % H;
   const long io = b * sio.bs + h * sio.hs;
-  bwd64_dq_block(q + io, k + io, v + io, dout + b * sdo.bs + h * sdo.hs,
-                 lse + bh * (long)S, delta + bh * (long)S, mask + b * (long)S,
-                 dq + b * sg.bs + h * sg.hs, S, kv_horizon(kv_len, b, S),
-                 blockIdx.x, causal, scale, has_mask, sio.rs, sdo.rs, sg.rs);
+  const long od = b * sdo.bs + h * sdo.hs;
+  bwd64_dq_block<DELTA>(
+      q + io, k + io, v + io, dout + od, lse + bh * (long)S,
+      delta + bh * (long)S, mask + b * (long)S, dq + b * sg.bs + h * sg.hs,
+      S, kv_horizon(kv_len, b, S), blockIdx.x, causal, scale, has_mask,
+      sio.rs, sdo.rs, sg.rs, o + od, delta + bh * (long)S);
 }
 
 }  // namespace
@@ -89,15 +99,26 @@ void attn_bwd64_launch(const bf16_t* q, const bf16_t* k, const bf16_t* v,
                        float scale, long B, long H, int S, StridesB sio,
                        StridesB sdo, StridesB sg, bf16_t* dq, bf16_t* dk,
                        bf16_t* dv, const int* kvl, hipStream_t stream) {
-  const long NR = B * H * (long)S;
-  hipLaunchKernelGGL((attn_bwd_delta_kernel<64>), dim3((NR * 8 + 255) / 256),
-                     dim3(256), 0, stream, dout, o, delta, S, H, NR, sdo);
   const dim3 block(256), grid((S + 127) / 128, B * H);
   const int c = causal ? 1 : 0, hm = mask ? 1 : 0;
+  // read at every call, so that one process can run both arms
+  const char* e = getenv("RAVNEST_ATTN_DELTA_FUSED");
+  const bool fused = e && e[0] == '1';
+  if (fused) {  // dq writes the Delta that kv reads
+    hipLaunchKernelGGL(attn_bwd64_dq_kernel<true>, grid, block, 0, stream, q,
+                       k, v, o, dout, lse, delta, mask, dq, S, c, scale, hm,
+                       H, sio, sdo, sg, kvl);
+  } else {
+    const long NR = B * H * (long)S;
+    hipLaunchKernelGGL((attn_bwd_delta_kernel<64>),
+                       dim3((NR * 8 + 255) / 256), dim3(256), 0, stream, dout,
+                       o, delta, S, H, NR, sdo);
+  }
   hipLaunchKernelGGL(attn_bwd64_kv_kernel, grid, block, 0, stream, q, k, v,
                      dout, lse, (const float*)delta, mask, dk, dv, S, c,
                      scale, hm, H, sio, sdo, sg, kvl);
-  hipLaunchKernelGGL(attn_bwd64_dq_kernel, grid, block, 0, stream, q, k, v,
-                     dout, lse, (const float*)delta, mask, dq, S, c, scale,
-                     hm, H, sio, sdo, sg, kvl);
+  if (!fused)
+    hipLaunchKernelGGL(attn_bwd64_dq_kernel<false>, grid, block, 0, stream, q,
+                       k, v, o, dout, lse, delta, mask, dq, S, c, scale, hm,
+                       H, sio, sdo, sg, kvl);
 }

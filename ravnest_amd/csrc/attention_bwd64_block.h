@@ -325,7 +325,12 @@ DEVINL void dq_stage(const DqRows& c, const char* sub, int k0, int q0,
 // dQ of q rows tile*128 .. +127 of one (sequence, head); a wave owns 32 of
 // them and loops the sequence's K/V stages up to the horizon. Pointers as
 // in bwd64_kv_block; dqp: the sequence's first dQ row of this head.
+// DELTA: the rows' Delta = rowsum(dO * O) is not read from dltp but
+// computed here, from the dO fragments the wave holds anyway and one read
+// of its O rows (op, row stride rs_do, in the fragment layout), and stored
+// to dlt_out for the kv kernel, which then has to run after this one.
 // -------------------------------------------------------------------
+template <bool DELTA = false>
 DEVINL void bwd64_dq_block(const bf16_t* __restrict__ qp,
                            const bf16_t* __restrict__ kp,
                            const bf16_t* __restrict__ vp,
@@ -335,7 +340,9 @@ DEVINL void bwd64_dq_block(const bf16_t* __restrict__ qp,
                            const float* __restrict__ mp,
                            bf16_t* __restrict__ dqp, int S, int L, int tile,
                            int causal, float scale, int has_mask, long rs_io,
-                           long rs_do, long rs_g) {
+                           long rs_do, long rs_g,
+                           const bf16_t* __restrict__ op = nullptr,
+                           float* __restrict__ dlt_out = nullptr) {
   __shared__ __attribute__((aligned(16))) char smem[2 * SLOTB];  // [K | V] x2
   const int lane = threadIdx.x & (WAVE - 1);
   const int hi = lane >> 5;
@@ -362,7 +369,25 @@ DEVINL void bwd64_dq_block(const bf16_t* __restrict__ qp,
   c.lane = lane; c.hi = hi; c.j32 = j32;
   c.scale = scale;
   c.l_row = (qrow < S) ? lsep[qrow] : -INFINITY;
-  c.dlt_row = (qrow < S) ? dltp[qrow] : 0.f;
+  if constexpr (DELTA) {
+    // the lane's 32 columns of its row in fp32, then the other half's lane
+    float dlt = 0.f;
+    if (qrow < S) {
+      const bf16_t* orp = op + (long)qrow * rs_do;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const bf16x8v of =
+            *reinterpret_cast<const bf16x8v*>(orp + s * 16 + hi * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dlt += (float)dof[s][j] * (float)of[j];
+      }
+    }
+    dlt += __shfl_xor(dlt, 32, WAVE);
+    if (hi == 0 && qrow < S) dlt_out[qrow] = dlt;
+    c.dlt_row = dlt;
+  } else {
+    c.dlt_row = (qrow < S) ? dltp[qrow] : 0.f;
+  }
 
   f32x16 dq_acc[2];
 #pragma unroll

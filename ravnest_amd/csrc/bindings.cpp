@@ -91,10 +91,12 @@ std::vector<at::Tensor> dropout_add_ln_fwd(at::Tensor z, at::Tensor a,
 std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
                                            at::Tensor w, at::Tensor mean,
                                            at::Tensor rstd,
-                                           at::Tensor maskbits, double p);
+                                           at::Tensor maskbits, double p,
+                                           c10::optional<at::Tensor> dy2);
 std::vector<at::Tensor> dropout_add_ln_bwd_dzsum(
     at::Tensor dy, at::Tensor s, at::Tensor w, at::Tensor mean,
-    at::Tensor rstd, at::Tensor maskbits, double p, bool dzsum_bf16);
+    at::Tensor rstd, at::Tensor maskbits, double p, bool dzsum_bf16,
+    c10::optional<at::Tensor> dy2);
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor targets,
                                int64_t ignore_index);
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
@@ -142,7 +144,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor lse, at::Tensor mask, bool causal,
                                  double scale,
                                  c10::optional<at::Tensor> kv_len,
-                                 c10::optional<bool> bwd64);
+                                 c10::optional<bool> bwd64,
+                                 c10::optional<at::Tensor> delta);
 std::vector<at::Tensor> attn_fwd_qkv(at::Tensor qkv, at::Tensor mask,
                                      bool causal, double scale,
                                      double pdrop, int64_t dseed,
@@ -154,7 +157,8 @@ at::Tensor attn_bwd_qkv(at::Tensor qkv, at::Tensor o, at::Tensor dout,
                         double scale, double pdrop,
                         c10::optional<at::Tensor> mbits,
                         c10::optional<at::Tensor> kv_len,
-                        c10::optional<bool> bwd64);
+                        c10::optional<bool> bwd64,
+                        c10::optional<at::Tensor> delta);
 at::Tensor attn_mask_kv_len(at::Tensor mask);
 at::Tensor attn_decode(at::Tensor qkv_new, at::Tensor k_cache,
                        at::Tensor v_cache, at::Tensor cache_len, double scale,
@@ -211,10 +215,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps"), py::arg("p"), py::arg("seed"),
         py::arg("seed_buf") = py::none());
   m.def("dropout_add_ln_bwd", &dropout_add_ln_bwd,
-        "fused dropout + residual add + LayerNorm bwd: dx, dz, dw, db");
+        "fused dropout + residual add + LayerNorm bwd: dx, dz, dw, db; the "
+        "upstream gradient is dy, or dy + dy2 summed in fp32",
+        py::arg("dy"), py::arg("s"), py::arg("w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("maskbits"), py::arg("p"),
+        py::arg("dy2") = py::none());
   m.def("dropout_add_ln_bwd_dzsum", &dropout_add_ln_bwd_dzsum,
         "dropout_add_ln_bwd and dzsum = dz.sum(0), fp32 or bf16: dx, dz, dw, "
-        "db, dzsum");
+        "db, dzsum",
+        py::arg("dy"), py::arg("s"), py::arg("w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("maskbits"), py::arg("p"),
+        py::arg("dzsum_bf16"), py::arg("dy2") = py::none());
   m.def("conv2d_fwd", &conv2d_fwd,
         "implicit-GEMM MFMA conv fwd (bf16 NCHW)", py::arg("x"),
         py::arg("w"), py::arg("bias") = py::none(), py::arg("st") = 1,
@@ -333,9 +344,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("dout"), py::arg("lse"), py::arg("mask"), py::arg("causal"),
         py::arg("scale"), py::arg("kv_len") = py::none(),
-        py::arg("bwd64") = py::none(),
+        py::arg("bwd64") = py::none(), py::arg("delta") = py::none(),
         "flash attention bwd (bf16, MFMA); bwd64: D=64 kernels on 64-row "
-        "stages (true) or 32-row tiles (false), none = RAVNEST_ATTN_BWD64");
+        "stages (true) or 32-row tiles (false), none = RAVNEST_ATTN_BWD64; "
+        "delta: fp32 (B*H*S) buffer to use for Delta = rowsum(dO * O)");
   m.def("attn_fwd_qkv", &attn_fwd_qkv,
         py::arg("qkv"), py::arg("mask"), py::arg("causal"),
         py::arg("scale"), py::arg("pdrop") = 0.0, py::arg("dseed") = 0,
@@ -347,6 +359,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mask"), py::arg("causal"), py::arg("scale"),
         py::arg("pdrop") = 0.0, py::arg("mbits") = py::none(),
         py::arg("kv_len") = py::none(), py::arg("bwd64") = py::none(),
+        py::arg("delta") = py::none(),
         "flash attention bwd, packed qkv -> dqkv");
   m.def("attn_mask_kv_len", &attn_mask_kv_len, py::arg("mask"),
         "additive (B,S) padding mask -> int32[B] key horizon");

@@ -3,6 +3,7 @@
 //   forward :  d = bf16(dropout(z));  s = bf16(a + d);  y = LN(s)
 //   backward:  dx = dLN(dy, s);  dz = keep ? bf16(bf16(dx) * scale) : 0;
 //              dw = sum_rows dy * xhat;  db = sum_rows dy
+//   (with a second gradient: dy + dy2 in fp32, dz = keep ? bf16(dx * scale))
 //
 // Both roundings of the composed path (dropout_fwd, then layernorm_add_fwd)
 // are reproduced, and the mask is the one dropout_fwd_kernel draws for the
@@ -255,13 +256,18 @@ __global__ __launch_bounds__(FWD_THREADS) void dropout_add_ln_fwd_kernel(
 // plain 16-byte reads and writes, in row order, so there is no race and
 // the sum is deterministic. VPL = 8 (H > 1024) would need more than 64 KiB
 // of LDS for that and sums in registers.
-template <typename PT, int VPL, bool FULL, bool DZS = false>
+// DY2: the upstream gradient arrives as two addends (the two consumers of a
+// residual-stream tensor); the row's gradient is float(dy) + float(dy2),
+// not rounded to bf16 in between, and autograd's add kernel (two reads and
+// a write of the whole tensor) becomes one more read here. dz is then
+// bf16(dx * scale) from the fp32 dx, not from the stored bf16 dx.
+template <typename PT, int VPL, bool FULL, bool DZS = false, bool DY2 = false>
 __global__ __launch_bounds__(BWD_THREADS)
 __attribute__((amdgpu_waves_per_eu(VPL <= 3 ? 4 : 1)))
 void dropout_add_ln_bwd_kernel(
-    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ s,
-    const PT* __restrict__ w, const float* __restrict__ mean,
-    const float* __restrict__ rstd,
+    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ dy2,
+    const bf16_t* __restrict__ s, const PT* __restrict__ w,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
     const unsigned char* __restrict__ maskbits, bf16_t* __restrict__ dx,
     bf16_t* __restrict__ dz, float* __restrict__ part, int H, long N,
     float scale) {
@@ -272,6 +278,7 @@ void dropout_add_ln_bwd_kernel(
   constexpr int ZV = ZREG ? VPL : 1;
   constexpr bool HOIST = VPL <= 4;
   constexpr int PV = HOIST ? VPL : 1;
+  constexpr int DV = DY2 ? VPL : 1;
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const int wpb = blockDim.x / WAVE;
@@ -311,13 +318,15 @@ void dropout_add_ln_bwd_kernel(
 
   for (long row = (long)blockIdx.x * wpb + wid; row < N; row += nwaves) {
     const long base = row * H;
-    u32x2 vd[VPL], vx[VPL];
+    u32x2 vd[VPL], vd2[DV], vx[VPL];
     unsigned int mb[VPL];
 #pragma unroll
     for (int k = 0; k < VPL; ++k) {
       const int g = lane + WAVE * k;
       if (FULL || g < G) {
         vd[k] = *reinterpret_cast<const u32x2*>(dy + base + 4 * g);
+        if constexpr (DY2)
+          vd2[k] = *reinterpret_cast<const u32x2*>(dy2 + base + 4 * g);
         vx[k] = *reinterpret_cast<const u32x2*>(s + base + 4 * g);
         mb[k] = maskbits[(base >> 3) + (g >> 1)];
       }
@@ -339,6 +348,12 @@ void dropout_add_ln_bwd_kernel(
         }
         float df[4], xf[4];
         unpack4(vd[k], df);
+        if constexpr (DY2) {
+          float d2[4];
+          unpack4(vd2[k], d2);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) df[j] += d2[j];
+        }
         unpack4(vx[k], xf);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -367,8 +382,11 @@ void dropout_add_ln_bwd_kernel(
         for (int j = 0; j < 4; ++j)
           o[j] = rs * (gv[k][j] - xh[k][j] * c1 - c2);
         const u32x2 ox = pack4(o);
-        // dz is rounded from the bf16 dx, as dropout_bwd sees it
-        unpack4(ox, o);
+        // dz is rounded from the bf16 dx, as dropout_bwd sees it. With two
+        // addends there is no composed path to reproduce, and dz comes from
+        // the fp32 dx: one rounding, so that its error stays below that of
+        // the route through a bf16 sum element by element, not on average
+        if constexpr (!DY2) unpack4(ox, o);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           o[j] = ((nib >> j) & 1) ? o[j] * scale : 0.f;
@@ -489,10 +507,10 @@ template <int VPL, bool DZS>
 constexpr size_t bwd_lds_floats(int H) {
   return (size_t)(!DZS ? 2 : VPL <= 4 ? 2 + BWD_THREADS / WAVE : 3) * H;
 }
-template <typename PT, int VPL, bool FULL, bool DZS>
+template <typename PT, int VPL, bool FULL, bool DZS, bool DY2>
 int bwd_resident_blocks() {
   static const int n = resident_blocks(
-      dropout_add_ln_bwd_kernel<PT, VPL, FULL, DZS>, BWD_THREADS,
+      dropout_add_ln_bwd_kernel<PT, VPL, FULL, DZS, DY2>, BWD_THREADS,
       bwd_lds_floats<VPL, DZS>(VPL * 256) * sizeof(float));
   return n;
 }
@@ -591,13 +609,20 @@ std::vector<at::Tensor> dropout_add_ln_fwd(at::Tensor z, at::Tensor a,
 }
 
 // zs: 0 = {dx, dz, dw, db}; 1 / 2 = those and the column sums of dz as
-// fp32 / bf16
+// fp32 / bf16. dy2: a second addend of the upstream gradient (DY2)
 static std::vector<at::Tensor> dropout_add_ln_bwd_impl(
-    at::Tensor dy, at::Tensor s, at::Tensor w, at::Tensor mean,
-    at::Tensor rstd, at::Tensor maskbits, double p, int zs) {
+    at::Tensor dy, c10::optional<at::Tensor> dy2, at::Tensor s, at::Tensor w,
+    at::Tensor mean, at::Tensor rstd, at::Tensor maskbits, double p, int zs) {
   check_common(s, w, "dropout_add_ln_bwd");
   check_common(dy, w, "dropout_add_ln_bwd");
   TORCH_CHECK(dy.sizes() == s.sizes() && aligned8(dy) && aligned8(s));
+  const bf16_t* dy2p = nullptr;
+  if (dy2.has_value()) {
+    check_common(*dy2, w, "dropout_add_ln_bwd");
+    TORCH_CHECK(dy2->sizes() == s.sizes() && aligned8(*dy2) &&
+                dy2->device() == dy.device());
+    dy2p = reinterpret_cast<const bf16_t*>(dy2->data_ptr());
+  }
   const int H = s.size(-1);
   const long N = s.numel() / H;
   TORCH_CHECK(mean.is_cuda() && mean.scalar_type() == at::kFloat &&
@@ -632,17 +657,19 @@ static std::vector<at::Tensor> dropout_add_ln_bwd_impl(
   at::Tensor part;
   int nparts = 0;
 
-#define DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, DZS)                             \
+#define DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, DZS, DY2)                        \
   do {                                                                      \
     nparts = (int)std::min<long>(                                           \
-        want, bwd_resident_blocks<PT, VPL, FULL, DZS>());                   \
+        want, bwd_resident_blocks<PT, VPL, FULL, DZS, DY2>());              \
     part = at::empty({nparts, ns * H}, s.options().dtype(at::kFloat));      \
-    hipLaunchKernelGGL((dropout_add_ln_bwd_kernel<PT, VPL, FULL, DZS>),     \
+    hipLaunchKernelGGL(                                                     \
+        (dropout_add_ln_bwd_kernel<PT, VPL, FULL, DZS, DY2>),               \
                        dim3(nparts),                                        \
                        dim3(BWD_THREADS),                                   \
                        (bwd_lds_floats<VPL, DZS>(H)) * sizeof(float),       \
                        stream,                                              \
                        reinterpret_cast<const bf16_t*>(dy.data_ptr()),      \
+                       dy2p,                                                \
                        reinterpret_cast<const bf16_t*>(s.data_ptr()),       \
                        reinterpret_cast<const PT*>(w.data_ptr()),           \
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),      \
@@ -661,8 +688,10 @@ static std::vector<at::Tensor> dropout_add_ln_bwd_impl(
                      H, nparts, ns)
 #define DAL_LAUNCH_BWD(PT, VPL, FULL)                                       \
   do {                                                                      \
-    if (zs) DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, true);                       \
-    else DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, false);                         \
+    if (zs && dy2p) DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, true, true);         \
+    else if (zs) DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, true, false);           \
+    else if (dy2p) DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, false, true);         \
+    else DAL_LAUNCH_BWD_MAIN(PT, VPL, FULL, false, false);                  \
     if (zs == 2) DAL_LAUNCH_BWD_FIN(PT, bf16_t);                            \
     else DAL_LAUNCH_BWD_FIN(PT, float);                                     \
   } while (0)
@@ -679,15 +708,17 @@ static std::vector<at::Tensor> dropout_add_ln_bwd_impl(
 std::vector<at::Tensor> dropout_add_ln_bwd(at::Tensor dy, at::Tensor s,
                                            at::Tensor w, at::Tensor mean,
                                            at::Tensor rstd,
-                                           at::Tensor maskbits, double p) {
-  return dropout_add_ln_bwd_impl(dy, s, w, mean, rstd, maskbits, p, 0);
+                                           at::Tensor maskbits, double p,
+                                           c10::optional<at::Tensor> dy2) {
+  return dropout_add_ln_bwd_impl(dy, dy2, s, w, mean, rstd, maskbits, p, 0);
 }
 
 // dropout_add_ln_bwd and dzsum = dz.sum(0) (fp32 sums of the stored bf16
 // values), returned as fp32 or bf16: {dx, dz, dw, db, dzsum}
 std::vector<at::Tensor> dropout_add_ln_bwd_dzsum(
     at::Tensor dy, at::Tensor s, at::Tensor w, at::Tensor mean,
-    at::Tensor rstd, at::Tensor maskbits, double p, bool dzsum_bf16) {
-  return dropout_add_ln_bwd_impl(dy, s, w, mean, rstd, maskbits, p,
+    at::Tensor rstd, at::Tensor maskbits, double p, bool dzsum_bf16,
+    c10::optional<at::Tensor> dy2) {
+  return dropout_add_ln_bwd_impl(dy, dy2, s, w, mean, rstd, maskbits, p,
                                  dzsum_bf16 ? 2 : 1);
 }

@@ -164,28 +164,47 @@ class BertLayer(nn.Module):
         return (self.fused_bias_grad and torch.is_tensor(a)
                 and _plain_biased_linear(lin) and ln.takes_zbias(a, lin))
 
-    def forward(self, x, mask, cu_seqlens=None, tiles=None):
+    @staticmethod
+    def _ln_pair(ln, a, z, **kw):
+        # (y, y) of ln(a, z): one y for the next sublayer and one for the
+        # next residual add, so that the LayerNorm backward gets their two
+        # gradients apart and adds them itself (ops/dropout_ln.py pair).
+        # Not while fx-tracing (as in _bias_downstream): traced graphs keep
+        # the module call and its single output.
+        if torch.is_tensor(a):
+            return ln(a, z, pair=True, **kw)
+        y = ln(a, z, **kw)
+        return y, y
+
+    def forward(self, x, mask, cu_seqlens=None, tiles=None, residual=None,
+                pair_out: bool = False):
+        """residual: the previous layer's second output (pair_out), x again
+        for the residual add; pair_out: return the (y, y) pair of ln2 for
+        the next layer's (x, residual) instead of y alone."""
+        r = x if residual is None else residual
         # attn.out -> ln1 and mlp_out -> ln2: the LayerNorm backward sums
         # dz for the projection's bias (ops/dropout_ln.py zbias)
         if cu_seqlens is not None:  # packed (T,C) stream, see BertForMLM
             kw = dict(cu_seqlens=cu_seqlens, tiles=tiles)
             if self._bias_downstream(self.ln1, x, self.attn.out):
-                x = self.ln1(x, self.attn(x, None, True, **kw),
-                             zbias=self.attn.out.bias)
+                x, r = self._ln_pair(self.ln1, r,
+                                     self.attn(x, None, True, **kw),
+                                     zbias=self.attn.out.bias)
             else:
-                x = self.ln1(x, self.attn(x, None, **kw))
+                x, r = self._ln_pair(self.ln1, r, self.attn(x, None, **kw))
         elif self._bias_downstream(self.ln1, x, self.attn.out):
-            x = self.ln1(x, self.attn(x, mask, out_bias_downstream=True),
-                         zbias=self.attn.out.bias)
+            x, r = self._ln_pair(
+                self.ln1, r, self.attn(x, mask, out_bias_downstream=True),
+                zbias=self.attn.out.bias)
         else:
-            x = self.ln1(x, self.attn(x, mask))
+            x, r = self._ln_pair(self.ln1, r, self.attn(x, mask))
+        ln2 = self._ln_pair if pair_out else \
+            (lambda ln, a, z, **kw: ln(a, z, **kw))
         if self._bias_downstream(self.ln2, x, self.mlp_out):
-            x = self.ln2(x, _linear_bias_downstream(self.mlp_out,
-                                                    self.mlp_in(x)),
-                         zbias=self.mlp_out.bias)
-        else:
-            x = self.ln2(x, self.mlp_out(self.mlp_in(x)))
-        return x
+            return ln2(self.ln2, r, _linear_bias_downstream(self.mlp_out,
+                                                            self.mlp_in(x)),
+                       zbias=self.mlp_out.bias)
+        return ln2(self.ln2, r, self.mlp_out(self.mlp_in(x)))
 
 
 class BertMLMHead(nn.Module):
@@ -231,9 +250,16 @@ class BertForMLM(nn.Module):
         m = (1.0 - attention_mask.to(torch.float32)) * -10000.0
         m = m.unsqueeze(1).unsqueeze(2)
         x = self.embeddings(input_ids)
-        for layer in self.layers:
-            x = layer(x, m)
-        return x
+        return self._run_layers(x, m)
+
+    def _run_layers(self, x, m, **kw):
+        # every layer but the last hands its output on as a pair: one for
+        # the next layer's attention, one for its residual add
+        # (BertLayer.forward pair_out)
+        r = None
+        for layer in self.layers[:-1]:
+            x, r = layer(x, m, residual=r, pair_out=True, **kw)
+        return self.layers[-1](x, m, residual=r, **kw)
 
     def forward(self, input_ids, attention_mask):
         return self.head(self._encode(input_ids, attention_mask))
@@ -249,9 +275,7 @@ class BertForMLM(nn.Module):
         emb = self.embeddings
         x = emb.drop(emb.ln(emb.word(ids) + emb.position(pos)))
         tiles = varlen_tiles(cu_seqlens, ids.shape[0])
-        for layer in self.layers:
-            x = layer(x, None, cu_seqlens=cu_seqlens, tiles=tiles)
-        return x
+        return self._run_layers(x, None, cu_seqlens=cu_seqlens, tiles=tiles)
 
     def forward_packed(self, ids, pos, cu_seqlens):
         """Packed ids, pos (T,) and cu_seqlens int32 (B+1,) of

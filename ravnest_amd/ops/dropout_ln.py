@@ -27,6 +27,17 @@ backward returns the column sums of dz (fp32 sums of the stored bf16
 values, written in b's dtype) as its gradient. Fused path only: asking for
 it where the composed path would run is an error, since nothing else would
 produce that gradient (DropoutAddLayerNorm.takes_zbias tells beforehand).
+
+pair: a residual-stream tensor y has two consumers, the next sublayer's
+first Linear and the next DropoutAddLayerNorm's residual input, and the
+autograd engine adds their two gradients with a kernel of its own (two
+reads and a write of the whole tensor) before it calls this op's backward.
+DropoutAddLayerNorm.forward(..., pair=True) returns y twice, as two outputs
+of the Function that alias one buffer: one per consumer. The engine then
+hands backward the two gradients apart, and the backward kernel reads both
+and adds them in fp32 (csrc/dropout_ln.hip DY2). On the composed path the
+pair is the same tensor twice and autograd adds as before.
+RAVNEST_LN_BWD_DY2=0 (read at construction) makes it that everywhere.
 """
 from __future__ import annotations
 
@@ -58,9 +69,15 @@ class _DropoutAddLayerNormFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dy2=None):
+        if dy is None:
+            dy, dy2 = dy2, None
+        if dy is None:  # pair: neither output reached the loss
+            return (None,) * 7
         s, weight, mean, rstd, maskbits = ctx.saved_tensors
         ext = get_ext(required=True)
+        if dy2 is not None:
+            dy2 = dy2.contiguous()
         # dx and dz are two distinct tensors out of one pass (autograd may
         # steal either for in-place accumulation)
         need = ctx.needs_input_grad
@@ -68,13 +85,26 @@ class _DropoutAddLayerNormFn(torch.autograd.Function):
         if need[6]:
             dx, dz, dw, db, dzsum = ext.dropout_add_ln_bwd_dzsum(
                 dy.contiguous(), s, weight, mean, rstd, maskbits, ctx.p,
-                ctx.zbias_dtype == torch.bfloat16)
+                ctx.zbias_dtype == torch.bfloat16, dy2)
         else:
             dx, dz, dw, db = ext.dropout_add_ln_bwd(
-                dy.contiguous(), s, weight, mean, rstd, maskbits, ctx.p)
+                dy.contiguous(), s, weight, mean, rstd, maskbits, ctx.p, dy2)
         return (dx if need[0] else None, dz if need[1] else None,
                 dw if need[2] else None, db if need[3] else None,
                 None, None, dzsum)
+
+
+class _DropoutAddLayerNormPairFn(_DropoutAddLayerNormFn):
+    """y twice, as two outputs on one buffer (module docstring, pair):
+    backward gets one gradient per consumer, either of them None when that
+    consumer is absent or frozen."""
+
+    @staticmethod
+    def forward(ctx, a, z, weight, bias, eps, p, zbias):
+        y = _DropoutAddLayerNormFn.forward(ctx, a, z, weight, bias, eps, p,
+                                           zbias)
+        ctx.set_materialize_grads(False)
+        return y, y.view_as(y)
 
 
 def _fusable(a, z, weight, bias) -> bool:
@@ -94,19 +124,23 @@ def _zbias_ok(zbias, H) -> bool:
 
 def dropout_add_layer_norm(a, z, weight, bias, eps: float = 1e-12,
                            p: float = 0.1, training: bool = True,
-                           fused: bool = True, zbias=None):
-    """y = LayerNorm(a + dropout(z, p)); a is the residual input. zbias:
-    see the module docstring."""
+                           fused: bool = True, zbias=None,
+                           pair: bool = False):
+    """y = LayerNorm(a + dropout(z, p)); a is the residual input. zbias,
+    pair (then the result is (y, y)): see the module docstring."""
     if fused and training and 0.0 < p < 1.0 and _fusable(a, z, weight, bias):
         if zbias is None or _zbias_ok(zbias, a.shape[-1]):
-            return _DropoutAddLayerNormFn.apply(
+            fn = _DropoutAddLayerNormPairFn if pair \
+                else _DropoutAddLayerNormFn
+            return fn.apply(
                 a.contiguous(), z.contiguous(), weight, bias, eps, p, zbias)
     if zbias is not None:
         raise RuntimeError(
             "dropout_add_layer_norm: zbias needs the fused path (training, "
             "0 < p < 1, CUDA bf16 activations, a fp32 or bf16 bias of the "
             "hidden size)")
-    return add_layer_norm(a, dropout(z, p, training), weight, bias, eps)
+    y = add_layer_norm(a, dropout(z, p, training), weight, bias, eps)
+    return (y, y) if pair else y
 
 
 class DropoutAddLayerNorm(nn.Module):
@@ -121,6 +155,7 @@ class DropoutAddLayerNorm(nn.Module):
         self.eps = eps
         self.p = p
         self.fused = os.environ.get("RAVNEST_FUSED_DROPOUT_LN", "1") != "0"
+        self.pair_grads = os.environ.get("RAVNEST_LN_BWD_DY2", "1") != "0"
 
     def takes_zbias(self, a, lin) -> bool:
         """True when forward(a, z, zbias=lin.bias) will take the fused
@@ -136,7 +171,14 @@ class DropoutAddLayerNorm(nn.Module):
                 and _fusable(a, a, self.weight, self.bias)
                 and _zbias_ok(b, a.shape[-1]))
 
-    def forward(self, a, z, zbias=None):
+    def forward(self, a, z, zbias=None, pair: bool = False):
+        """pair: return (y, y), one per consumer of y (module docstring);
+        with RAVNEST_LN_BWD_DY2=0 the two are one tensor."""
+        if pair and not self.pair_grads:
+            y = dropout_add_layer_norm(a, z, self.weight, self.bias,
+                                       self.eps, self.p, self.training,
+                                       self.fused, zbias)
+            return y, y
         return dropout_add_layer_norm(a, z, self.weight, self.bias, self.eps,
                                       self.p, self.training, self.fused,
-                                      zbias)
+                                      zbias, pair)
